@@ -7,12 +7,15 @@ One "step" = one batch of same-size images per GPU through the whole device chai
 N > 1: one process per GPU (torchrun), every rank its own images, fixed-size detection records all-gathered over RCCL/xGMI
 every step (north_star); weak scaling.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3                      # the headline: configs[1]
+    python bench.py --gpus 1 --steps 20 --warmup 3                      # the headline: configs[1], nothing else measured
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               # + other configs, batch-1 latency, variants, roofline, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's detections as DIR/*.npy
     python bench.py --config c3|c4|c5 ...                                # the other BASELINE.json configs (committed lines in profiles/)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement; extra objects `roofline`, `stages`, `cpu_baseline`).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), config; with --full also
+`roofline`, `stages`, `telemetry`, `x3_variant`, `f32_mfma_variant`, `cpu_baseline`, `latency_ms_batch1`, `other_configs`.
 /root/reference is never read here.
 """
 import argparse
@@ -294,7 +297,7 @@ def train_bench(args, c, dev, world, rank, dist):
     torch.cuda.synchronize()
     ar_host0 = (getattr(ar, "host_s", 0.0), getattr(ar, "sends", 0))
     t0 = time.perf_counter()
-    sw.train_model(args.steps, verbose=False)
+    sess.timed_losses = sw.train_model(args.steps, verbose=False)      # total loss of every timed step (read back after the last one)
     sess.host_enqueue_s = sw.enqueue_s                      # the host's share: launches enqueued, GPU not yet waited for (rounds 3-4 stopped
     # this clock after train_model's final loss read-back, i.e. after a device synchronisation: it read the step time)
     sess.all_reduce_host = None if ar is None else (getattr(ar, "host_s", 0.0) - ar_host0[0], getattr(ar, "sends", 0) - ar_host0[1])
@@ -382,10 +385,10 @@ def run_timed(step, steps, warmup, dist=None, sync=None, between=None):
 
 def child_line(extra, timeout_s):
     """One short run of this script in a child process (its own cfg globals / Session / graphs), returns its parsed JSON line or an
-    {"error": ...} record.  Used by the default N = 1 invocation to put the other BASELINE configs and the batch-1 latency into the
+    {"error": ...} record.  Used by an N = 1 --full invocation to put the other BASELINE configs and the batch-1 latency into the
     driver-observed line; the parent's timed region is over by then and its buffers simply stay resident beside the child's."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-f32-variant", "--no-other-configs"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-f32-variant", "--no-other-configs"] + list(extra)
     t0 = time.time()
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s, env=dict(os.environ, MASTER_PORT=str(29500 + os.getpid() % 2000 + 1)))
@@ -438,6 +441,35 @@ def other_configs(budget_s, t_start):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 stays float64, integers become float64), at most
+    DUMP_LIMIT_BYTES in all.  Returns {name: shape}."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64 if a.dtype.kind in "iub" else np.float32))
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in conv.items()}
+
+
+def detection_outputs(dets, counts):
+    """The caller's view of one detection step: dets [B, REC_ROWS, 6] (x1, y1, x2, y2, score, class) with the rows past each image's
+    count zeroed (they are not part of the result), counts [B]."""
+    dets = dets.detach().cpu().numpy().astype(np.float32).copy()
+    counts = counts.detach().cpu().numpy().astype(np.int64)
+    for b, n in enumerate(counts):
+        dets[b, int(n):] = 0.0
+    return {"detections": dets, "detection_counts": counts.astype(np.float64)}
+
+
 def train_roofline(by_pipe, step_s, gflop_ref):
     """Roofline object of the training step, priced like the inference line: frac = sum over launches (FLOPs_i / dense peak of the pipe
     launch i issues on) / step time -- the fraction of the matrix pipes' peak the issued instruction mix reaches over the WHOLE timed step
@@ -465,7 +497,13 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2", help="BASELINE.json config (default c2 = configs[1], the metric's)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--profile-steps", type=int, default=3, help="steps of the HIP-event pass that feeds `roofline` / `stages`")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the other BASELINE configs and the batch-1 "
+                    "latency (child runs), the x3-only / all-f32-MFMA variants, clock / power telemetry, the HIP-event pass behind "
+                    "`roofline` / `stages` and the CPU baseline.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(the arrays its caller receives) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--profile-steps", type=int, default=None, help="steps of the HIP-event pass that feeds `roofline` / `stages` "
+                    "(default 3 with --full or --layer-report, else 0)")
     ap.add_argument("--batch", type=int, default=0, help="images per launch chain: the launches of B images are shared (fills the 256 "
                     "CUs on the 38x63 layers); a step still counts images.  0 = the config's default")
     ap.add_argument("--streams", type=int, default=0, help="launch chains in flight per GPU (independent HIP streams + graphs)")
@@ -495,6 +533,8 @@ def main():
     ap.add_argument("--skip-calls", default="", help="MEASUREMENT ONLY (the energy ledger, scratch/energy_ledger.py): comma-separated C-ABI entry names "
                     "(prefix match) whose launches are dropped -- the results are WRONG by construction and the line says so (`ablated`)")
     args = ap.parse_args()
+    if args.profile_steps is None:
+        args.profile_steps = 3 if (args.full or args.layer_report) else 0
     c = CONFIGS[args.config]
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -504,11 +544,11 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.gpus > 1 and world == 1:
         raise SystemExit("N>1 must be launched with torch.distributed.run (one process per GPU)")
-    # The default N = 1 invocation also reports the other BASELINE configs and the batch-1 latency (child runs of this script).  They
+    # An N = 1 --full invocation also reports the other BASELINE configs and the batch-1 latency (child runs of this script).  They
     # run FIRST, before this process creates its GPU context: two processes with live queues on one GPU are time-sliced by the
     # scheduler, which costs a child 5-25 % (measured: 5.30 vs 4.26 ms latency with the parent's context alive).
     appended = None
-    if world == 1 and args.config == "c2" and not args.no_other_configs and not args.no_graph and not (args.batch or args.streams):
+    if args.full and world == 1 and args.config == "c2" and not args.no_other_configs and not args.no_graph and not (args.batch or args.streams):
         appended = other_configs(75, time.time())
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -577,6 +617,8 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"total_loss": np.array(sess.timed_losses[-1:], dtype=np.float64)})
         if rank == 0:
             value = world * args.steps / elapsed
             out = dict(common, value=round(value, 3), ms_per_step=round(1000.0 * elapsed / args.steps, 4),
@@ -669,6 +711,16 @@ def main():
             prev = t
     elapsed = timed_region()
     host_enqueue_s = getattr(run_timed, "enqueue_s", 0.0)       # (of the timed region that counts: a graph launch per step and chain)
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on chain (steps - 1) % S; read before any later pass reuses its buffers.  N > 1: the all-gathered
+        # records of every rank, which is what each rank's caller holds after the step
+        last = (args.steps - 1) % S
+        if world > 1:
+            g = gathered[last].reshape(world * B, parallel.REC_FLOATS)
+            outs = detection_outputs(g[:, :parallel.REC_ROWS * 6].unflatten(1, (parallel.REC_ROWS, 6)), g[:, parallel.REC_ROWS * 6])
+        else:
+            outs = detection_outputs(views[last], counts[last])
+        dump_outputs(args.dump_outputs, outs)
     exchange_ok = None
     if world > 1:
         # self-check of the collective, untimed: one more step on every chain, then every rank verifies every slot (a wrong or stale
@@ -710,9 +762,9 @@ def main():
                                                                      nb / (ms * 1e-3) / 1e9 if ms > 0 else 0))
 
     f32_variant, x3_variant, telemetry = None, None, None
-    if world == 1 and not args.no_graph:
+    if args.full and world == 1 and not args.no_graph:
         telemetry = Telemetry(Telemetry.pci_of(dev)).run(lambda: [timed_region() for _ in range(3)])      # clock / power of the shipped configuration
-    if args.mfma in ("h2", "x3") and world == 1 and not args.no_f32_variant and not args.no_graph:
+    if args.full and args.mfma in ("h2", "x3") and world == 1 and not args.no_f32_variant and not args.no_graph:
         # the same workload on the other pipe choices, timed in the same run (rank 0, N = 1 like cpu_baseline)
         keep = (cfg.HIP.MFMA_H2, cfg.HIP.MFMA_X3)
         if args.mfma == "h2":
@@ -877,7 +929,7 @@ def main():
                                    "achieved_GBs": round(nb / (ms * 1e-3) / 1e9, 1) if ms > 0 else None,
                                    "frac_of_hbm_peak": round(nb / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if ms > 0 else None}
             out["stages"] = stages
-        if world == 1 and not args.no_cpu_baseline and c["net"] == "res101":
+        if args.full and world == 1 and not args.no_cpu_baseline and c["net"] == "res101":
             out["cpu_baseline"] = cpu_baseline(sess.variables, image, c)
         if appended is not None:
             oc = appended

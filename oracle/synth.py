@@ -96,3 +96,17 @@ def threshold_pairs(n_pairs=24, seed=3, thr=0.5, filler=200):
     out = np.vstack([d, fill]).astype(f32)
     out[:, 4] = tie_free(out[:, 4], rng)
     return out[rng.permutation(out.shape[0])]
+
+
+def threshold_dets(k, thr, cluster, seed):
+    """random_dets(k, seed, cluster) with up to 24 box pairs engineered to sit on the NMS threshold: box i becomes 100 x 100 px
+    (+1 rule) and box i + 1 the same box cut to width 100 thr, so that inter / union == thr in float32 (unsorted)."""
+    d = random_dets(k, seed=seed, cluster=cluster)
+    rng = np.random.RandomState(seed)
+    for i in rng.choice(k, size=min(24, k // 4), replace=False):
+        x1, y1 = np.floor(d[i, 0]), np.floor(d[i, 1])
+        d[i, :4] = (x1, y1, x1 + 99, y1 + 99)
+        j = (i + 1) % k
+        w = int(round(100 * thr / 1.0))
+        d[j, :4] = (x1, y1, x1 + w - 1, y1 + 99)
+    return d

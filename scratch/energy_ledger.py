@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 steps = int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else 30
 out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "gpurun_out", "r06_energy_ledger.txt")
-COMMON = ["--no-cpu-baseline", "--no-other-configs", "--no-f32-variant", "--profile-steps", "0", "--steps", str(steps), "--warmup", "3"]
+COMMON = ["--full", "--no-cpu-baseline", "--no-other-configs", "--no-f32-variant", "--profile-steps", "0", "--steps", str(steps), "--warmup", "3"]
 
 
 def run(label, extra, ablation=False):

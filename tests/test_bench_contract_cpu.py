@@ -89,3 +89,31 @@ def test_train_mode_tile_threshold_rule():
         assert Network.h2_min_tiles("TRAIN") == 150
     finally:
         cfg.HIP.H2_MIN_TILES, cfg.HIP.H2_TRAIN_MIN_TILES = keep
+
+
+def test_plain_run_is_lean_and_dumps_what_the_caller_receives(tmp_path):
+    """A plain run measures the headline only; everything else is behind --full.  --dump-outputs writes the last timed step's arrays as
+    float32 / float64 .npy files, within the size limit, with rows past each image's detection count zeroed."""
+    import numpy as np
+    import torch
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    for gate in ("if args.full and world == 1 and args.config == \"c2\"", "if args.full and world == 1 and not args.no_graph:",
+                 "if args.full and args.mfma in", "if args.full and world == 1 and not args.no_cpu_baseline"):
+        assert gate in src, gate
+    b = _bench()
+    dets = torch.arange(2 * 4 * 6, dtype=torch.float32).reshape(2, 4, 6) + 1
+    outs = b.detection_outputs(dets, torch.tensor([3, 0], dtype=torch.int32))
+    assert outs["detections"].dtype == np.float32 and outs["detection_counts"].dtype == np.float64
+    assert np.array_equal(outs["detections"][0, :3], dets[0, :3].numpy()) and not outs["detections"][0, 3:].any()
+    assert not outs["detections"][1].any() and outs["detection_counts"].tolist() == [3.0, 0.0]
+    shapes = b.dump_outputs(str(tmp_path / "d"), dict(outs, ints=np.arange(5, dtype=np.int32)))
+    assert shapes == {"detections": [2, 4, 6], "detection_counts": [2], "ints": [5]}
+    assert np.load(str(tmp_path / "d" / "ints.npy")).dtype == np.float64
+    assert np.array_equal(np.load(str(tmp_path / "d" / "detections.npy")), outs["detections"])
+    try:
+        b.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(b.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+        raise AssertionError("limit not enforced")
+    except RuntimeError:
+        pass
+    assert not os.path.exists(str(tmp_path / "big"))

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import frcnn_oracle as ora
+import gen_golden_ref_gpu_nms as gen_ref
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -111,9 +112,9 @@ def test_nms_sorted_and_host_compat__nms(dev):
     assert keep_h[:n_h.value].tolist() == ora.gpu_nms(ds, 0.3)             # the CUDA kernel's rule (nms_kernel.cu:71), float threshold
 
 
-def test_nms_under_the_reference_mangled_name(dev):
+def test_nms_under_the_reference_mangled_name(dev, golden):
     """The reference's `_nms` has C++ linkage (lib/nms/gpu_nms.hpp:1-2, bound by lib/nms/gpu_nms.pyx:13-31): libfrcnn_hip.so exports
-    `_Z4_nmsPiS_PKfiifi` too, bound here exactly the way _ref_gpu_nms binds the reference's own build -- same keep list as the
+    `_Z4_nmsPiS_PKfiifi` too, bound here exactly the way oracle/gen_golden_ref_gpu_nms.py binds the reference's own build -- same keep list as the
     extern "C" name and as the CUDA kernel's rule."""
     import ctypes
     import frcnn_hip
@@ -126,57 +127,42 @@ def test_nms_under_the_reference_mangled_name(dev):
     fn(keep.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), ds.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(3000), ctypes.c_int(5),
        ctypes.c_float(0.3), ctypes.c_int(0))
     assert keep[:n.value].tolist() == ora.gpu_nms(ds, 0.3)
-    ref = _ref_gpu_nms("libref_gpu_nms.so")
-    assert keep[:n.value].tolist() == ref(ds, 0.3)
+    assert keep[:n.value].tolist() == _ref_gpu_nms_keep(golden, "plain", ds, 0.3)
 
 
-def _ref_gpu_nms(name):
-    """The reference's CUDA kernel + host loop, hipified and compiled from /root/reference/lib/nms/nms_kernel.cu by
-    oracle/build_ref.py::build_gpu_nms into oracle/_ref/nms/ (the binaries travel with the snapshot)."""
-    import ctypes
-    import os
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "nms", name)
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/nms/%s not built (python oracle/build_ref.py where /root/reference exists)" % name)
-    fn = ctypes.CDLL(path)._Z4_nmsPiS_PKfiifi
-    fn.restype = None
-
-    def run(ds, thresh):
-        keep = np.zeros(ds.shape[0], dtype=np.int32)
-        n = ctypes.c_int(0)
-        fn(keep.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n), np.ascontiguousarray(ds, dtype=f32).ctypes.data_as(ctypes.c_void_p),
-           ctypes.c_int(ds.shape[0]), ctypes.c_int(ds.shape[1]), ctypes.c_float(thresh), ctypes.c_int(0))
-        return keep[:n.value].tolist()
-    return run
+def _ref_gpu_nms_keep(golden, key, ds, thresh, fma=False):
+    """The keep list of the reference's CUDA kernel + host loop (lib/nms/nms_kernel.cu, hipified and compiled for gfx950 by
+    oracle/build_ref.py::build_gpu_nms; FMA-contracted build with fma=True) on `ds`, as stored in tests/golden/ref_gpu_nms.npz by
+    oracle/gen_golden_ref_gpu_nms.py.  The stored input digest must match `ds`.  Where that build is present under oracle/_ref/nms/,
+    its live result must equal the stored one as well."""
+    g = golden["ref_gpu_nms"]
+    assert str(g["plain_sha1" if key == "plain" else "sha1_" + key]) == gen_ref.digest(ds), "inputs differ from the stored case " + key
+    want = g[("fma_" if fma else "keep_") + key if key != "plain" else "plain_keep"].tolist()
+    live = gen_ref.ref_lib("libref_gpu_nms_fma.so" if fma else "libref_gpu_nms.so")
+    if live is not None:
+        assert live(ds, thresh).tolist() == want, "oracle/_ref/nms build differs from tests/golden/ref_gpu_nms.npz"
+    return want
 
 
 @pytest.mark.parametrize("k,thr,cl,seed", [(3000, 0.3, 12, 11), (6000, 0.7, 40, 3), (12000, 0.7, 200, 5), (257, 0.5, 3, 2), (64, 0.3, 1, 9)])
-def test_gpu_rule_bit_exact_vs_the_reference_cuda_kernel(dev, k, thr, cl, seed):
+def test_gpu_rule_bit_exact_vs_the_reference_cuda_kernel(dev, golden, k, thr, cl, seed):
     """FRCNN_NMS_RULE_GPU (`_nms`, what nms_wrapper picks under cfg.USE_GPU_NMS) against the reference's OWN CUDA kernel
-    (lib/nms/nms_kernel.cu:24-144, hipified + compiled for gfx950 into oracle/_ref, separate roundings): identical keep lists,
-    incl. boxes engineered to sit on the threshold.  The FMA-contracted build of the same file (what nvcc's default -fmad=true may
-    produce) is run beside it: where it differs, the product follows the un-contracted arithmetic of lib/nms/py_cpu_nms.py:18-38."""
+    (lib/nms/nms_kernel.cu:24-144, hipified + compiled for gfx950 into oracle/_ref, separate roundings; its keep lists stored in
+    tests/golden/ref_gpu_nms.npz): identical keep lists, incl. boxes engineered to sit on the threshold.  The FMA-contracted build of
+    the same file (what nvcc's default -fmad=true may produce) is reported beside it: where it differs, the product follows the
+    un-contracted arithmetic of lib/nms/py_cpu_nms.py:18-38."""
     import ctypes
     import frcnn_hip
-    ref, ref_fma = _ref_gpu_nms("libref_gpu_nms.so"), _ref_gpu_nms("libref_gpu_nms_fma.so")
-    d = synth.random_dets(k, seed=seed, cluster=cl)
-    # pairs exactly at the threshold: box j = box i shrunk so that IoU == thr in float32 for several i
-    rng = np.random.RandomState(seed)
-    for i in rng.choice(k, size=min(24, k // 4), replace=False):
-        x1, y1 = np.floor(d[i, 0]), np.floor(d[i, 1])
-        d[i, :4] = (x1, y1, x1 + 99, y1 + 99)                          # 100 x 100 px with the +1 rule
-        j = (i + 1) % k
-        w = int(round(100 * thr / 1.0))                                 # inter / union = (w * 100) / (100 * 100) = thr when w = 100 thr
-        d[j, :4] = (x1, y1, x1 + w - 1, y1 + 99)
-    order = ora.order_desc(d[:, 4])
-    ds = np.ascontiguousarray(d[order])
+    key = gen_ref.case_key(k, thr, cl, seed)
+    # pairs exactly at the threshold: box j = box i shrunk so that IoU == thr in float32 for several i (synth.threshold_dets)
+    ds = gen_ref.threshold_case(k, thr, cl, seed)
     keep_h = np.zeros(k, dtype=np.int32)
     n_h = ctypes.c_int(0)
     frcnn_hip.lib()._nms(keep_h.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_h), ds.ctypes.data_as(ctypes.c_void_p), k, 5,
                          ctypes.c_float(thr), 0)
     got = keep_h[:n_h.value].tolist()
-    want = ref(ds, thr)
-    fma = ref_fma(ds, thr)
+    want = _ref_gpu_nms_keep(golden, key, ds, thr)
+    fma = _ref_gpu_nms_keep(golden, key, ds, thr, fma=True)
     print("k %d thr %.1f: kept %d; reference CUDA kernel (contract off) %d, FMA-contracted build %d (differs in %d positions)"
           % (k, thr, len(got), len(want), len(fma), sum(1 for a, b in zip(want, fma) if a != b) + abs(len(want) - len(fma))))
     assert got == want

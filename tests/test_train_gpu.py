@@ -585,3 +585,81 @@ def test_snapshot_restore_is_bit_identical_for_mobilenet_and_vgg16(dev, tmp_path
             assert np.array_equal(restored[k], at_snapshot[k]), k
     finally:
         cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.BG_THRESH_LO, cfg.TRAIN.LEARNING_RATE, cfg.TRAIN.SNAPSHOT_ITERS, cfg.TRAIN.DISPLAY = old
+
+
+def test_train_step_at_odd_feature_sizes_matches_torch_autograd(dev):
+    """The ResNet-50 training step on a 136x202 image: the trained stages run on 34x51, 17x26 and 9x13 maps (block2/unit_4's conv2 is a
+    stride-2 3x3 with one odd and one even side), so odd stride-2 data gradients, asymmetric up_pad and ragged last rows / columns are
+    all on the path.  Three sweep policies (winograd, h2, pipe_dgrads) = (F,F,T), (T,T,T), (T,T,F), knobs as in
+    test_full_train_step_matches_torch_autograd; EVERY trainable parameter's gradient and bias vs torch float64 autograd at 2e-3.  A counting
+    wrapper on ops.call shows that the three together launched each data-gradient route of tests/test_dgrad_gpu.py."""
+    from dense_ref import TrainRef
+    from frcnn_hip import ops
+    from frcnn_hip.runtime import Session
+    from frcnn_hip.train import TrainState
+    from model.config import cfg
+    from nets.resnet_v1 import resnetv1
+    SC, RT = (4, 8, 16), (0.5, 1, 2)
+    H, W = 136, 202
+    heads = {21, 84, 18, 36}
+    seen = set()
+    old = (cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.BG_THRESH_LO, cfg.HIP.WINOGRAD_TRAIN)
+    old_h2 = (cfg.HIP.H2_TRAIN, cfg.HIP.H2_MIN_TILES, cfg.HIP.H2_TRAIN_MIN_TILES)
+    real = ops.call
+    try:
+        for wino, h2, pipe in ((False, False, True), (True, True, True), (True, True, False)):
+            cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.BG_THRESH_LO, cfg.HIP.WINOGRAD_TRAIN = 64, 0.0, wino
+            cfg.HIP.H2_TRAIN, cfg.HIP.H2_MIN_TILES = bool(h2), (1 if h2 else old_h2[1])
+            cfg.HIP.H2_TRAIN_MIN_TILES = None if h2 else old_h2[2]
+            sess = Session(device=dev, seed=5)
+            net = resnetv1(num_layers=50)
+            net.create_architecture("TRAIN", 21, tag="odd_w%d_h%d_p%d" % (wino, h2, pipe), anchor_scales=SC, anchor_ratios=RT)
+            sess.init_variables(net.variable_specs())
+            rng = np.random.RandomState(3)
+            image = ((rng.rand(1, H, W, 3) * 255.0).astype(np.float32) - cfg.PIXEL_MEANS.astype(np.float32)) * np.float32(1 / 256.0)
+            gt = np.array([[16, 16, 79, 79, 3], [60, 30, 150, 110, 7], [5, 70, 60, 130, 12]], dtype=np.float32)
+            blobs = dict(data=image, im_info=np.array([H, W, 1.0], dtype=np.float32), gt_boxes=gt)
+            losses = net.train_forward(sess, blobs)
+            pt, at = net._proposal_targets, net._anchor_targets
+            ts = TrainState(sess, net, momentum=0.9, weight_decay=1e-4).build()
+            ts.winograd = (4, 64, True) if wino else None
+            ts.h2_train = 1 if h2 else None
+            ts.pipe_dgrads = pipe
+            ts.wgrad_tn, ts.wgrad_h2, ts.wgrad_stream = wino, h2, (2 if wino else 0)
+            trace = []
+
+            def counting(name, *a):
+                trace.append((name, a))
+                return real(name, *a)
+            ops.call = counting
+            try:
+                ts.backward(net._loss_seeds)
+            finally:
+                ops.call = real
+            torch.cuda.synchronize()
+            names = [n for n, _ in trace]
+            seen.update(names)
+            for i, (n, a) in enumerate(trace):      # the padded-head route: a head filter transposed and padded, then the conv kernel
+                if n == "frcnn_transpose_pad" and a[1] in heads and a[4] == (a[1] + 31) // 32 * 32:
+                    nxt = [m for m in names[i + 1:] if m != "frcnn_transpose_pad"][:1]
+                    if nxt and nxt[0].startswith("frcnn_conv2d_nhwc"):
+                        seen.add("padded_head_route")
+            ref = TrainRef(sess.variables, 50, 21, SC, RT, net.trainable_scope)
+            to_np = lambda d_: {k: v.cpu().numpy() for k, v in d_.items()}
+            rl = ref.losses(image, pt["rois"].cpu().numpy(), to_np(at), to_np(pt))
+            for k in ("rpn_cross_entropy", "rpn_loss_box", "cross_entropy", "loss_box"):
+                assert abs(losses[k].item() - rl[k].item()) <= 1e-4 * max(1.0, abs(rl[k].item())), (wino, h2, pipe, k)
+            sum(rl.values()).backward()
+            scopes = [sc[len(net._scope):] for sc in ts.params]
+            assert len(scopes) > 40 and any("/block2/unit_4/" in s for s in scopes)
+            try:
+                _check_param_grads(net, ts, ref, scopes)
+            except AssertionError as e:
+                raise AssertionError("policy (winograd, h2, pipe_dgrads) = %s: %s" % ((wino, h2, pipe), e))
+    finally:
+        ops.call = real
+        cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.BG_THRESH_LO, cfg.HIP.WINOGRAD_TRAIN = old
+        cfg.HIP.H2_TRAIN, cfg.HIP.H2_MIN_TILES, cfg.HIP.H2_TRAIN_MIN_TILES = old_h2
+    want = {"frcnn_conv2d_dgrad_strided", "frcnn_gemm_h2_masked", "frcnn_add_strided", "padded_head_route"}
+    assert want <= seen, sorted(want - seen)
+    assert seen & {"frcnn_winograd_output_transform_masked", "frcnn_winograd7_output_transform_masked"}

@@ -63,3 +63,48 @@ def test_conv2d_wgrad_refuses_what_it_does_not_cover(dev):
     out = torch.zeros((21, 1, 1, 64), dtype=torch.float32, device=dev)
     with pytest.raises(FrcnnHipError):
         ops.conv2d_wgrad(gy, x, 1, 1, 1, (0, 0, 0, 0), out)
+
+
+def _block4_operands(R_, Cin, Cout, seed):
+    """the shipped block4 conv3's operands: dY = spatial_mean_bwd of a per-RoI gradient (constant over each RoI's 49 pixels), RoIs of
+    magnitudes 2^-8 .. 2^8 (fg vs bg), gated by the ReLU mask of conv3's output; X post-ReLU with a few outlier channels"""
+    rng = np.random.RandomState(seed)
+    g = rng.randn(R_, 1, 1, Cout) * 2.0 ** rng.randint(-8, 9, size=(R_, 1, 1, 1)) / 49.0
+    gy = (np.broadcast_to(g, (R_, 7, 7, Cout)) * (rng.rand(R_, 7, 7, Cout) < 0.5)).astype(np.float32)
+    x = np.maximum(rng.randn(R_, 7, 7, Cin), 0)
+    x[..., rng.choice(Cin, size=8, replace=False)] *= 64.0
+    return gy, x.astype(np.float32)
+
+
+@pytest.mark.parametrize("h2", [False, True], ids=["f32", "h2"])
+def test_conv2d_wgrad_block4_conv3_structured_operands(dev, h2):
+    """block4/unit_3 conv3 as shipped (M = 256 RoIs x 49, Cin 512, Cout 2048, 1x1) on block4-tail operands: the 2e-6 bound of the
+    cases above; elementwise |got - want| <= 16 2^-23 B (B = the float64 product of |dY| and |X|); and for h2 the f32 class against
+    the f32 TN kernel on the same data (error / 2^-23 B at most 3x, plus a floor of 1e-7 of the scale).  k_wgrad_h2 scales each
+    (channel, 64-pixel slab) block of dY, and a slab spans two RoIs whose magnitudes differ by up to 2^16."""
+    import dgrad_ref as R
+    from frcnn_hip import ops
+    R_, Cin, Cout = 256, 512, 2048
+    gy, x = _block4_operands(R_, Cin, Cout, 11)
+    pad = (0, 0, 0, 0)
+    want = R.wgrad64(gy, x, 1, 1, 1, pad)
+    B = R.wgrad64(np.abs(gy), x, 1, 1, 1, pad)
+    got = {}
+    for hh in ((False, True) if h2 else (False,)):
+        out = torch.full((Cout, 1, 1, Cin), float("nan"), dtype=torch.float32, device=dev)
+        ops.conv2d_wgrad(torch.from_numpy(gy).to(dev), torch.from_numpy(x).to(dev), 1, 1, 1, pad, out, h2=hh)
+        torch.cuda.synchronize()
+        got[hh] = out.cpu().numpy().astype(np.float64)
+    g = got[h2]
+    err = np.abs(g - want).max() / np.abs(want).max()
+    r = R.ratio(g, want, B)
+    line = "wgrad %s block4 conv3 structured: max err / max |dW| = %.2e, max |err| / (2^-23 B) = %.3f" % ("h2 " if h2 else "f32", err, r)
+    if h2:
+        r32 = R.ratio(got[False], want, B)
+        e32 = np.abs(got[False] - want).max() / np.abs(want).max()
+        line += "; f32 TN %.3f (max-rel %.2e), h2 / f32 = %.2f" % (r32, e32, r / max(r32, 1e-30))
+    print(line)
+    assert np.isfinite(g).all() and err <= 2e-6, err
+    assert r <= 16.0, r
+    if h2:
+        assert r <= 3.0 * r32 + 1e-7 / R.EPS, (r, r32)

@@ -68,7 +68,8 @@ __C = AttrDict(
     ANCHOR_SCALES=[8, 16, 32], ANCHOR_RATIOS=[0.5, 1, 2], RPN_CHANNELS=512,
     # device-path switches (no reference counterpart): Winograd F(m x m,3x3) for the 3x3 stride-1 convolutions at test
     # time; m = WINOGRAD_M (4 or 2) except scopes containing a WINOGRAD_F2_SCOPES token, which use m = 2.  WINOGRAD_TRAIN: also in
-    # the training step (forward and data gradient of those layers; filters transformed on the device every step).
+    # the training step (forward and data gradient of those layers; filters transformed on the device every step).  WINOGRAD_DGRAD False:
+    # the data gradients of those layers on the direct f32 kernel instead (the forward keeps WINOGRAD_TRAIN).
     # Shipped policy (profiles/r02_fullsize_parity.txt): F(2x2,3x3) in block1 / block2 -- the early layers, whose activations carry a
     # large common mean, are where the F(4x4,3x3) transforms lose digits (full-size head error 1.8x the float32 control with F(4,3)
     # everywhere, 1.0x with this policy, for 1.2 % of throughput); F(4x4,3x3) in block3 / RPN / block4 (7x7 scheme).
@@ -128,7 +129,7 @@ __C = AttrDict(
     # reference's graph takes any [1, H, W, 3] (lib/nets/network.py:386-390) and an imdb has hundreds of sizes: memory is bounded by these
     # caps, not by the imdb.  ResNet-101 at 600 x 1000 holds ~2 GB per shape.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
-             WINOGRAD_TRAIN=True,
+             WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,

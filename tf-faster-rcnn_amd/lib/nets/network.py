@@ -931,7 +931,7 @@ class Network(object):
     def configure_train_op(train_op):
         """cfg.HIP -> the solver handle's switches for the reverse sweep (frcnn_hip/train.py)."""
         train_op.winograd = ((int(cfg.HIP.WINOGRAD_M), int(cfg.HIP.WINOGRAD_MIN_CIN), bool(cfg.HIP.WINOGRAD_7X7))
-                             if (cfg.HIP.WINOGRAD and cfg.HIP.WINOGRAD_TRAIN) else None)
+                             if (cfg.HIP.WINOGRAD and cfg.HIP.WINOGRAD_TRAIN and cfg.HIP.WINOGRAD_DGRAD) else None)
         train_op.h2_train = Network.h2_min_tiles("TRAIN") if (cfg.HIP.MFMA_H2 and cfg.HIP.H2_TRAIN) else None
         train_op.wgrad_stream = int(cfg.HIP.WGRAD_STREAM)
         train_op.wgrad_tn = bool(cfg.HIP.WGRAD_TN)

@@ -256,6 +256,14 @@ long long frcnn_snappy_uncompress(const unsigned char* src, size_t n, unsigned c
 int frcnn_prep_image_shape(int h, int w, int target_size, int max_size, double* im_scale, int* out_h, int* out_w);
 int frcnn_prep_image(const void* src_d, int src_is_float, int h, int w, const double* pixel_means, double im_scale, float* out_d,
                      int OH, int OW, int out_c, void* stream);
+/* The training minibatch of one roidb entry on device (lib/roi_data_layer/minibatch.py:19-74, lib/utils/blob.py:33-47):
+ * frcnn_prep_image with the source mirrored first iff `flipped` (im[:, ::-1, :]: column x is read at w-1-x), plus rows [0,G) of
+ * the static gt buffer gt_d [>=G][5] from the entry's boxes_d uint16 [G][4] and classes_d int32 [G]: coordinate =
+ * (float)((double)box * im_scale), class converted to float (G = 0: no gt launch, the three pointers may be NULL).
+ * OH/OW/im_scale from frcnn_prep_image_shape(h, w, cfg.TRAIN.SCALES[i], cfg.TRAIN.MAX_SIZE). */
+int frcnn_prep_train_image(const void* src_d, int src_is_float, int h, int w, int flipped, const double* pixel_means, double im_scale,
+                           float* out_d, int OH, int OW, int out_c, const unsigned short* boxes_d, const int* classes_d, int G,
+                           float* gt_d, void* stream);
 
 /* G independent NT GEMMs in one launch (f32 MFMA): y[g][m][n] = sum_k x[g][m][k] * w[g][n][k];  K % 32 == 0. */
 int frcnn_gemm_batched_nt(const float* x_d, const float* w_d, float* y_d, int G, int M, int N, int K, void* stream);

@@ -29,7 +29,10 @@ extern "C" int frcnn_prep_image_shape(int h, int w, int target_size, int max_siz
 
 struct Mean3 { double b, g, r; };
 
-template <typename SRC>
+// FLIP: the source is read mirrored (minibatch.py:63-64 `im[:, ::-1, :]` before anything else): mirrored column x is stored column
+// w-1-x.  The tap arithmetic is unchanged, so a wave still reads its taps from the same few cache lines, in descending order.
+// VEC4 (OC == 4 and a 16-byte aligned output, chosen by the launcher): one 16-byte store per lane, a wave writes 1 KiB contiguous.
+template <typename SRC, bool FLIP, bool VEC4>
 __global__ void k_prep_image(const SRC* __restrict__ src, int h, int w, Mean3 mean, double scale_inv, int OH, int OW, int OC,
                              float* __restrict__ out) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
@@ -49,20 +52,38 @@ __global__ void k_prep_image(const SRC* __restrict__ src, int h, int w, Mean3 me
   const int y0 = min(max(sy, 0), h - 1), y1 = min(max(sy + 1, 0), h - 1);
   const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
   const int x1 = last ? sx : sx + 1;
+  const int c0 = FLIP ? w - 1 - sx : sx, c1 = FLIP ? w - 1 - x1 : x1;      // stored columns of the two taps
   const double m[3] = {mean.b, mean.g, mean.r};
   float* o = out + ((size_t)oy * OW + ox) * OC;
+  float v[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     // im.astype(float32) - PIXEL_MEANS (float64) assigned in place to float32: float64 subtraction, one rounding
-    const float p00 = (float)((double)src[((size_t)y0 * w + sx) * 3 + c] - m[c]);
-    const float p01 = (float)((double)src[((size_t)y0 * w + x1) * 3 + c] - m[c]);
-    const float p10 = (float)((double)src[((size_t)y1 * w + sx) * 3 + c] - m[c]);
-    const float p11 = (float)((double)src[((size_t)y1 * w + x1) * 3 + c] - m[c]);
+    const float p00 = (float)((double)src[((size_t)y0 * w + c0) * 3 + c] - m[c]);
+    const float p01 = (float)((double)src[((size_t)y0 * w + c1) * 3 + c] - m[c]);
+    const float p10 = (float)((double)src[((size_t)y1 * w + c0) * 3 + c] - m[c]);
+    const float p11 = (float)((double)src[((size_t)y1 * w + c1) * 3 + c] - m[c]);
     const float r0 = last ? p00 * 1.0f : p00 * a0 + p01 * a1;
     const float r1 = last ? p10 * 1.0f : p10 * a0 + p11 * a1;
-    o[c] = r0 * b0 + r1 * b1;
+    v[c] = r0 * b0 + r1 * b1;
   }
-  if (OC == 4) o[3] = 0.f;
+  if (VEC4) {
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], 0.f);
+  } else {
+    o[0] = v[0], o[1] = v[1], o[2] = v[2];
+    if (OC == 4) o[3] = 0.f;
+  }
+}
+
+template <typename SRC, bool FLIP>
+static void launch_prep(const void* src_d, int h, int w, const double* pixel_means, double im_scale, float* out_d, int OH, int OW, int out_c,
+                        hipStream_t stream) {
+  const Mean3 mean = {pixel_means[0], pixel_means[1], pixel_means[2]};
+  const dim3 grid((OW + 255) / 256, OH), block(256);
+  if (out_c == 4 && ((size_t)out_d & 15) == 0)
+    hipLaunchKernelGGL((k_prep_image<SRC, FLIP, true>), grid, block, 0, stream, (const SRC*)src_d, h, w, mean, 1.0 / im_scale, OH, OW, out_c, out_d);
+  else
+    hipLaunchKernelGGL((k_prep_image<SRC, FLIP, false>), grid, block, 0, stream, (const SRC*)src_d, h, w, mean, 1.0 / im_scale, OH, OW, out_c, out_d);
 }
 
 // src_d: BGR [h][w][3], uint8 (src_is_float = 0) or float32 (1).  pixel_means: HOST double[3] (B,G,R; config.py PIXEL_MEANS).
@@ -71,14 +92,46 @@ extern "C" int frcnn_prep_image(const void* src_d, int src_is_float, int h, int 
                                 float* out_d, int OH, int OW, int out_c, void* stream) {
   if (!src_d || !pixel_means || !out_d || h <= 0 || w <= 0 || OH <= 0 || OW <= 0 || !(im_scale > 0)) return FRCNN_E_ARG;
   if (out_c != 3 && out_c != 4) return FRCNN_E_UNSUPPORTED;
-  const Mean3 mean = {pixel_means[0], pixel_means[1], pixel_means[2]};
-  const dim3 grid((OW + 255) / 256, OH), block(256);
   if (src_is_float)
-    hipLaunchKernelGGL(k_prep_image<float>, grid, block, 0, (hipStream_t)stream, (const float*)src_d, h, w, mean, 1.0 / im_scale, OH, OW,
-                       out_c, out_d);
+    launch_prep<float, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
   else
-    hipLaunchKernelGGL(k_prep_image<unsigned char>, grid, block, 0, (hipStream_t)stream, (const unsigned char*)src_d, h, w, mean,
-                       1.0 / im_scale, OH, OW, out_c, out_d);
+    launch_prep<unsigned char, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
   LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// minibatch.py:44-46: gt_boxes[:, 0:4] = boxes (uint16) * im_scale (Python float) -> float64 product, rounded once into the float32 blob;
+// gt_boxes[:, 4] = gt_classes (int32).  One thread per row.
+__global__ void k_fill_gt(const unsigned short* __restrict__ boxes, const int* __restrict__ classes, int G, double im_scale,
+                          float* __restrict__ gt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= G) return;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) gt[i * 5 + k] = (float)((double)boxes[i * 4 + k] * im_scale);
+  gt[i * 5 + 4] = (float)classes[i];
+}
+
+// The training minibatch of ONE roidb entry (lib/roi_data_layer/minibatch.py:19-74 + lib/utils/blob.py:33-47) staged on device:
+// frcnn_prep_image on the source mirrored iff `flipped`, and rows [0,G) of the static gt buffer gt_d [>=G][5] from the entry's
+// boxes_d uint16 [G][4] / classes_d int32 [G] (a second tiny launch on the same stream; G = 0: skipped, pointers may be NULL).
+extern "C" int frcnn_prep_train_image(const void* src_d, int src_is_float, int h, int w, int flipped, const double* pixel_means,
+                                      double im_scale, float* out_d, int OH, int OW, int out_c, const unsigned short* boxes_d,
+                                      const int* classes_d, int G, float* gt_d, void* stream) {
+  if (!src_d || !pixel_means || !out_d || h <= 0 || w <= 0 || OH <= 0 || OW <= 0 || !(im_scale > 0) || G < 0) return FRCNN_E_ARG;
+  if (G > 0 && (!boxes_d || !classes_d || !gt_d)) return FRCNN_E_ARG;
+  if (out_c != 3 && out_c != 4) return FRCNN_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (src_is_float) {
+    if (flipped) launch_prep<float, true>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, st);
+    else launch_prep<float, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, st);
+  } else {
+    if (flipped) launch_prep<unsigned char, true>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, st);
+    else launch_prep<unsigned char, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, st);
+  }
+  LAUNCH_CHECK();
+  if (G > 0) {
+    hipLaunchKernelGGL(k_fill_gt, dim3((G + 63) / 64), dim3(64), 0, st, boxes_d, classes_d, G, im_scale, gt_d);
+    LAUNCH_CHECK();
+  }
   return FRCNN_OK;
 }

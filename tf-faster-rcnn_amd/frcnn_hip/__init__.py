@@ -72,6 +72,7 @@ SIGNATURES = {
     "frcnn_snappy_uncompress": (c_longlong, [_P, c_size_t, _P, c_size_t]),
     "frcnn_prep_image_shape": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P]),
     "frcnn_prep_image": (c_int, [_P, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P]),
+    "frcnn_prep_train_image": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "frcnn_gemm_batched_nt": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_winograd_filter_transform": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "frcnn_winograd_filter_transform_device": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),

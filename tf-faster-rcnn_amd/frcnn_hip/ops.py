@@ -491,6 +491,26 @@ def prep_image(im_d, pixel_means, im_scale, out_hw, out=None, out_c=4):
     return out
 
 
+def prep_train_image(im_d, flipped, pixel_means, im_scale, out_hw, out=None, out_c=4, boxes=None, classes=None, gt_out=None):
+    """One roidb entry's minibatch on device (roi_data_layer/minibatch.py): prep_image of the image mirrored first iff `flipped`, and --
+    boxes uint16 [G,4] / classes int32 [G] / gt_out float32 [>=G,5] given -- gt_out[:G] = (boxes * im_scale, classes)."""
+    assert im_d.is_cuda and im_d.is_contiguous() and im_d.dim() == 3 and im_d.shape[2] == 3
+    assert im_d.dtype in (torch.uint8, torch.float32)
+    h, w = im_d.shape[:2]
+    OH, OW = out_hw
+    out = _empty((1, OH, OW, out_c), dtype=torch.float32, device=im_d.device) if out is None else out
+    assert out.shape == (1, OH, OW, out_c) and out.is_contiguous() and out.dtype == torch.float32
+    G = 0 if boxes is None else int(boxes.shape[0])
+    if G:
+        assert boxes.dtype == torch.uint16 and boxes.shape == (G, 4) and boxes.is_cuda and boxes.is_contiguous()
+        assert classes.dtype == torch.int32 and classes.shape == (G,) and classes.is_cuda and classes.is_contiguous()
+        assert gt_out.dtype == torch.float32 and gt_out.dim() == 2 and gt_out.shape[0] >= G and gt_out.shape[1] == 5 and gt_out.is_contiguous()
+    means = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(pixel_means, dtype=np.float64).reshape(-1)[:3]])
+    call("frcnn_prep_train_image", _ptr(im_d), 1 if im_d.dtype == torch.float32 else 0, h, w, 1 if flipped else 0, means, float(im_scale),
+         _ptr(out), OH, OW, int(out_c), _ptr(boxes if G else None), _ptr(classes if G else None), G, _ptr(gt_out if G else None), _stream())
+    return out
+
+
 def winograd_filter_transform(w_hwio, scale=None, m=2):
     """HOST: 3x3 HWIO filter -> U [(m+2)^2, Cout, Cin] (F(m x m,3x3), optional folded per-output scale)."""
     w = np.ascontiguousarray(w_hwio, dtype=np.float32)

@@ -7,8 +7,10 @@ cfg.TRAIN.DISPLAY iterations in the reference's format (:298-302).  Data-paralle
 per rank per step, one bucketed RCCL all-reduce of the flat gradient buffer (new relative to the reference, which
 trains on a single GPU with IMS_PER_BATCH 1).  Checkpoints are TensorFlow V2 bundles read / written without TensorFlow
 (frcnn_hip/tensor_bundle.py): `initialize` = ImageNet weights + fix_variables (:177-202), `snapshot` = Saver.save of the
-variables, the Momentum slots and a `.pkl` with the iteration (:58-100), `restore` (:204-233).  roidb feeding / TensorBoard
-are out of scope; `data_layer` is any iterator of blobs {'data','im_info','gt_boxes'}."""
+variables, the Momentum slots and a `.pkl` with the iteration, the data layer's cursor / permutation and numpy's global random state
+(:58-100), `restore` (:204-233).  `get_training_roidb` / `filter_roidb` (:324-360) prepare a roidb for roi_data_layer.layer.RoIDataLayer.
+TensorBoard is out of scope; `data_layer` is any iterator of blobs {'data','im_info','gt_boxes'} (float image) or of
+RoIDataLayer's raw-image blobs (roi_data_layer/minibatch.py)."""
 import os
 import pickle
 import time
@@ -84,7 +86,8 @@ class SolverWrapper(object):
 
     def snapshot(self, it, output_dir):
         """train_val.py:58-100: `<prefix>_iter_<it>.ckpt` (variables + Momentum slots + global_step) and a .pkl with the
-        iteration (the reference also pickles numpy RNG / data-layer cursors; the sampling here is seeded per step)."""
+        iteration, the fg/bg sampling seed and -- for a roidb data layer -- its cursor, permutation and numpy's global random state (:60-78),
+        so that a resumed run continues with the same images."""
         if not self.write_snapshots:                             # data-parallel: rank 0 writes, the others only read
             return None, None
         os.makedirs(output_dir, exist_ok=True)
@@ -95,8 +98,12 @@ class SolverWrapper(object):
                 self.sess.variables[k] = v
         extra["global_step"] = np.array(it, dtype=np.int64)
         self.sess.save(base + '.ckpt', {k: v for k, v in extra.items() if k.endswith("/Momentum") or k == "global_step"})
+        meta = {'iter': it, 'sample_seed': int(self.net._sample_seed)}
+        if hasattr(self.data_layer, 'get_state'):
+            meta['data_layer'] = self.data_layer.get_state()
+            meta['np_random_state'] = np.random.get_state()
         with open(base + '.pkl', 'wb') as f:
-            pickle.dump({'iter': it, 'sample_seed': int(self.net._sample_seed)}, f, pickle.HIGHEST_PROTOCOL)
+            pickle.dump(meta, f, pickle.HIGHEST_PROTOCOL)
         print('Wrote snapshot to: {:s}'.format(base + '.ckpt'))
         self.np_paths.append(base + '.pkl')
         self.ss_paths.append(base + '.ckpt')
@@ -113,6 +120,9 @@ class SolverWrapper(object):
         with open(nfile, 'rb') as f:
             meta = pickle.load(f)
         self.net._sample_seed = meta.get('sample_seed', 0)        # the fg/bg sampling stream continues where it stopped
+        if 'data_layer' in meta and hasattr(self.data_layer, 'set_state'):     # (older snapshots carry neither key: the layer starts over)
+            self.data_layer.set_state(meta['data_layer'])
+            np.random.set_state(meta['np_random_state'])
         if sfile not in self.ss_paths:
             self.np_paths.append(nfile)
             self.ss_paths.append(sfile)
@@ -161,6 +171,31 @@ def synthetic_data_layer(num_classes, seed=3, height=600, width=1000, scale=1.6,
                       axis=1).astype(np.float32)
         image = ((rng.rand(1, height, width, 3) * 255.0).astype(np.float32) - cfg.PIXEL_MEANS.astype(np.float32)) * np.float32(image_gain)
         yield {'data': image, 'im_info': np.array([height, width, scale], dtype=np.float32), 'gt_boxes': gt}
+
+
+def get_training_roidb(imdb):
+    """train_val.py:324-335: the imdb's roidb, mirrored twins appended iff cfg.TRAIN.USE_FLIPPED, enriched by prepare_roidb."""
+    from roi_data_layer import roidb as rdl_roidb
+    if cfg.TRAIN.USE_FLIPPED:
+        print('Appending horizontally-flipped training examples...')
+        imdb.append_flipped_images()
+        print('done')
+    print('Preparing training data...')
+    rdl_roidb.prepare_roidb(imdb)
+    print('done')
+    return imdb.roidb
+
+
+def filter_roidb(roidb):
+    """train_val.py:338-360: drops the entries without any box that could become a foreground (max overlap >= FG_THRESH) or a
+    background (BG_THRESH_LO <= max overlap < BG_THRESH_HI) RoI -- for a gt roidb: the images without objects."""
+    def is_valid(entry):
+        ov = entry['max_overlaps']
+        return bool(np.any(ov >= cfg.TRAIN.FG_THRESH) or np.any((ov < cfg.TRAIN.BG_THRESH_HI) & (ov >= cfg.TRAIN.BG_THRESH_LO)))
+    num = len(roidb)
+    filtered_roidb = [entry for entry in roidb if is_valid(entry)]
+    print('Filtered {} roidb entries: {} -> {}'.format(num - len(filtered_roidb), num, len(filtered_roidb)))
+    return filtered_roidb
 
 
 def train_net(network, sess, data_layer, max_iters=40000, all_reduce=None, world_size=1, pretrained_model=None, output_dir=None,

@@ -740,11 +740,28 @@ class Network(object):
     def _stage_train_inputs(self, sess, blobs):
         """blobs -> the step's static input buffers: image [1,H,W,4] (like _stage_image), gt boxes in a [TRAIN_MAX_GT,5] buffer whose
         first G rows are valid (G is a launch argument of the two target layers, the only consumers), im_info as host floats (launch
-        arguments; part of a recorded step's key)."""
+        arguments; part of a recorded step's key).  A blob without 'data' is RoIDataLayer's raw-image form (roi_data_layer/minibatch.py):
+        the uint8 image and the roidb's uint16 boxes / int32 classes go to the device as they are and frcnn_prep_train_image writes both
+        static buffers there (mirror, mean, resize; boxes * im_scale)."""
         self._sess = sess
-        self._image = self._stage_image(sess, blobs["data"])
         info = blobs["im_info"]
         self._im_info = (float(info[0]), float(info[1]), float(info[2]))
+        if "data" not in blobs:
+            im = blobs["image"]
+            im_scale, OH, OW = self._train_prep_shape(blobs)
+            dev = sess.device
+            G = int(blobs["boxes"].shape[0])
+            cap = max(self.TRAIN_MAX_GT, (G + 63) // 64 * 64)
+            self._image = sess.buf(self._tag + "/image", (1, OH, OW, 4), zero=True)
+            buf = sess.buf(self._tag + "/gt_boxes", (cap, 5), zero=True)
+            im_d = torch.from_numpy(np.ascontiguousarray(im)).to(dev, non_blocking=True)
+            boxes_d = torch.from_numpy(np.ascontiguousarray(blobs["boxes"], dtype=np.uint16)).to(dev, non_blocking=True) if G else None
+            classes_d = torch.from_numpy(np.ascontiguousarray(blobs["gt_classes"], dtype=np.int32)).to(dev, non_blocking=True) if G else None
+            ops.prep_train_image(im_d, bool(blobs["flipped"]), cfg.PIXEL_MEANS, im_scale, (OH, OW), out=self._image, out_c=4,
+                                 boxes=boxes_d, classes=classes_d, gt_out=buf)
+            self._gt_boxes = buf[:G]
+            return
+        self._image = self._stage_image(sess, blobs["data"])
         gt = blobs["gt_boxes"]
         gt = gt if torch.is_tensor(gt) else torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32))
         G = int(gt.shape[0])
@@ -752,6 +769,12 @@ class Network(object):
         buf = sess.buf(self._tag + "/gt_boxes", (cap, 5), zero=True)
         buf[:G].copy_(gt, non_blocking=True)
         self._gt_boxes = buf[:G]
+
+    @staticmethod
+    def _train_prep_shape(blobs):
+        """(im_scale, OH, OW) of a raw-image blob: blob.py:37-45 for its target size (frcnn_prep_image_shape)."""
+        h, w = blobs["image"].shape[:2]
+        return ops.prep_image_shape(h, w, int(blobs["target_size"]), int(blobs.get("max_size", cfg.TRAIN.MAX_SIZE)))
 
     TRAIN_MAX_GT = 128          # rows of the static gt buffer (grows in steps of 64 for an image with more boxes: a new recorded-step key)
 
@@ -792,8 +815,12 @@ class Network(object):
         """A roidb's images differ in size from step to step (lib/roi_data_layer/layer.py:80-93); the step's activations, gradients, arena
         results and scratch are static per image SHAPE (a recorded step addresses them), so they live in the shape's buffer scope and at
         most cfg.HIP.TRAIN_CACHE_SHAPES shapes are kept -- the least recently used shape's buffers and recordings are dropped together."""
-        d = blobs["data"]
-        shape = (int(d.shape[0]), int(d.shape[1]), int(d.shape[2]), 4)
+        if "data" in blobs:
+            d = blobs["data"]
+            shape = (int(d.shape[0]), int(d.shape[1]), int(d.shape[2]), 4)
+        else:                                                # raw-image blob: the staged shape is the prep kernel's output shape
+            _, OH, OW = self._train_prep_shape(blobs)
+            shape = (1, OH, OW, 4)
         self._train_scope_key = ("train_shape", self._tag, shape)
         return sess.shape_scope(self._train_scope_key, group=("train", self._tag), cap=int(cfg.HIP.TRAIN_CACHE_SHAPES))
 

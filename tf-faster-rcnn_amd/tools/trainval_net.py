@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Train a Faster R-CNN network on the MI355X path -- entry point of the reference's tools/trainval_net.py:29-139
-with the same flags (--cfg --weight --imdb --imdbval --iters --tag --net --set).  Datasets / checkpoints are out
-of scope: `--imdb synthetic` feeds seeded synthetic images + gt boxes.  Multi-GPU:
-`python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/trainval_net.py ...` (one image per
-rank per step, bucketed RCCL all-reduce of the gradients)."""
+with the same flags (--cfg --weight --imdb --imdbval --iters --tag --net --set).  `--imdb voc_2007_trainval` (or `a+b`) trains
+on the roidb of `<cfg.DATA_DIR>/VOCdevkit<year>` through roi_data_layer.layer.RoIDataLayer: flipped twins iff cfg.TRAIN.USE_FLIPPED,
+snapshots under get_output_dir(imdb, tag) unless --output names another directory; `--imdb synthetic` (default) feeds seeded synthetic
+images + gt boxes and writes snapshots only with --output.  --imdbval is accepted and unused (the reference reads it for TensorBoard
+summaries only).  Multi-GPU: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/trainval_net.py ...` (one
+image per rank per step -- rank r of W takes minibatches r, r+W, ... of the one seeded stream -- bucketed RCCL all-reduce of the
+gradients)."""
 import argparse
 import os
 import pprint
@@ -15,8 +18,8 @@ import torch
 import _init_paths  # noqa: F401
 from frcnn_hip import parallel
 from frcnn_hip.runtime import Session
-from model.config import cfg, cfg_from_file, cfg_from_list
-from model.train_val import synthetic_data_layer, train_net
+from model.config import cfg, cfg_from_file, cfg_from_list, get_output_dir
+from model.train_val import filter_roidb, get_training_roidb, synthetic_data_layer, train_net
 from nets.resnet_v1 import resnetv1
 
 
@@ -24,8 +27,8 @@ def parse_args():
     parser = argparse.ArgumentParser(description='Train a Faster R-CNN network')
     parser.add_argument('--cfg', dest='cfg_file', help='optional config file', default=None, type=str)
     parser.add_argument('--weight', dest='weight', help='initialize with pretrained model weights (TF V2 checkpoint prefix, or .npz)', type=str)
-    parser.add_argument('--output', dest='output_dir', help='directory for snapshots (default: none written)', default=None, type=str)
-    parser.add_argument('--imdb', dest='imdb_name', help='dataset to train on', default='synthetic', type=str)
+    parser.add_argument('--output', dest='output_dir', help='directory for snapshots (default: output/<EXP_DIR>/<imdb>/<tag> for a dataset, none for synthetic)', default=None, type=str)
+    parser.add_argument('--imdb', dest='imdb_name', help='dataset to train on: synthetic | voc_<year>_<split>[+...]', default='synthetic', type=str)
     parser.add_argument('--imdbval', dest='imdbval_name', help='dataset to validate on', default='synthetic', type=str)
     parser.add_argument('--iters', dest='max_iters', help='number of iterations to train', default=70000, type=int)
     parser.add_argument('--tag', dest='tag', help='tag of the model', default=None, type=str)
@@ -35,6 +38,29 @@ def parse_args():
         parser.print_help()
         sys.exit(1)
     return parser.parse_args()
+
+
+def combined_roidb(imdb_names, verbose=True):
+    """trainval_net.py:63-85 of the reference: the training roidbs of `a+b+...` concatenated; the imdb of a combination carries the
+    joined name and the classes of its second member."""
+    import datasets.imdb
+    from datasets.factory import get_imdb
+    say = print if verbose else (lambda *a: None)
+
+    def get_roidb(imdb_name):
+        imdb = get_imdb(imdb_name)
+        say('Loaded dataset `{:s}` for training'.format(imdb.name))
+        imdb.set_proposal_method(cfg.TRAIN.PROPOSAL_METHOD)
+        say('Set proposal method: {:s}'.format(cfg.TRAIN.PROPOSAL_METHOD))
+        return get_training_roidb(imdb)
+
+    names = imdb_names.split('+')
+    roidbs = [get_roidb(s) for s in names]
+    roidb = roidbs[0]
+    for r in roidbs[1:]:
+        roidb.extend(r)
+    imdb = datasets.imdb.imdb(imdb_names, get_imdb(names[1]).classes) if len(names) > 1 else get_imdb(imdb_names)
+    return imdb, roidb
 
 
 if __name__ == '__main__':
@@ -58,7 +84,16 @@ if __name__ == '__main__':
     np.random.seed(cfg.RNG_SEED)
     if not args.net.startswith('res'):
         raise NotImplementedError('training is provided for the ResNet family (SURVEY.md 8a rows 14-17)')
-    num_classes = 21
+    out_dir = getattr(args, 'output_dir', None)
+    imdb = None
+    if args.imdb_name != 'synthetic':
+        imdb, roidb = combined_roidb(args.imdb_name)
+        print('{:d} roidb entries'.format(len(roidb)))
+        if out_dir is None:
+            out_dir = get_output_dir(imdb, args.tag)
+        print('Output will be saved to `{:s}`'.format(out_dir))
+        roidb = filter_roidb(roidb)
+    num_classes = 21 if imdb is None else imdb.num_classes
     sess = Session(seed=cfg.RNG_SEED)                                  # same weights on every rank
     net = resnetv1(num_layers=int(args.net[3:]))
     net.create_architecture("TRAIN", num_classes, tag='default', anchor_scales=cfg.ANCHOR_SCALES, anchor_ratios=cfg.ANCHOR_RATIOS)
@@ -68,8 +103,11 @@ if __name__ == '__main__':
         sess.load_variables(dict(np.load(args.weight)))
     elif args.weight:
         pretrained = args.weight                                        # ImageNet checkpoint: restore + fix_variables
-    data = synthetic_data_layer(num_classes, seed=cfg.RNG_SEED + 1000 * rank, image_gain=1.0 / 256.0)
-    out_dir = getattr(args, 'output_dir', None)
+    if imdb is None:
+        data = synthetic_data_layer(num_classes, seed=cfg.RNG_SEED + 1000 * rank, image_gain=1.0 / 256.0)
+    else:
+        from roi_data_layer.layer import RoIDataLayer
+        data = RoIDataLayer(roidb, num_classes, rank=rank, world_size=world)       # the same seeded stream on every rank
     # every rank resumes from the snapshots in out_dir (same weights, Momentum slots, iteration and sampling seed on all replicas);
     # only rank 0 writes new ones
     train_net(net, sess, data, max_iters=args.max_iters, all_reduce=all_reduce, world_size=world, pretrained_model=pretrained,

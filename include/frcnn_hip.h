@@ -201,6 +201,23 @@ int frcnn_bbox_transform(const float* ex_rois_d, const float* gt_rois_d, int N, 
 /* boxes_d [n,4] f64, query_d [k,4] f64 -> out_d [n,k] f64. */
 int frcnn_bbox_overlaps(const double* boxes_d, int n, const double* query_d, int k, double* out_d, void* stream);
 
+/* ---- COCO bbox evaluation, per (image, category) group: replaces the IoU + greedy matching of the published COCO evaluator
+ * (evaluateImg; lib/datasets/coco_eval.py states the protocol) ------------------------------------------------------------- */
+/* CSR over n_groups groups: det_off_d / gt_off_d [n_groups+1] int64; det_xywh_d [n_det,4] f64, per group already sorted by -score and
+ * cut to max_det; gt_xywh_d [n_gt,4] f64, gt_area_d [n_gt] f64 (annotation area), gt_crowd_d [n_gt] u8.  iou_thrs_d [T] f64,
+ * area_rng_d [A,2] f64 (both ends inclusive), A*T <= 64 (FRCNN_E_UNSUPPORTED beyond).  Outputs: det_matched_d / det_ignored_d [A][T][n_det]
+ * u8, gt_ignored_d [A][n_gt] u8, every element of every group with a detection or a gt written; iou_out_d (may be NULL) the f64 IoU of
+ * every pair, group after group, each group [D,G] row-major ("pair-CSR": offsets = running sum of D*G).  IoU on xywh without "+1",
+ * i / (crowd ? det area : det area + gt area - i), one rounding per operation.  ws must hold frcnn_coco_match_workspace_bytes() for
+ * the totals of the offsets passed (n_pairs = sum of D*G); the entry can only check ws_bytes against the part that depends on
+ * n_groups (the totals live on the device and it does not synchronise): a group whose slice would not fit is left unwritten rather than
+ * written out of bounds.  frcnn_hip.ops.coco_match derives the size from the host copy of the same offsets, so it cannot get there. */
+size_t frcnn_coco_match_workspace_bytes(int n_groups, long long n_det, long long n_gt, long long n_pairs);
+int frcnn_coco_match(const double* det_xywh_d, const long long* det_off_d, const double* gt_xywh_d, const double* gt_area_d,
+                     const unsigned char* gt_crowd_d, const long long* gt_off_d, int n_groups, const double* iou_thrs_d, int T,
+                     const double* area_rng_d, int A, unsigned char* det_matched_d, unsigned char* det_ignored_d,
+                     unsigned char* gt_ignored_d, double* iou_out_d, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense ops (the TF/slim call sites of lib/nets/network.py:323-378, resnet_v1.py:80-125,
  * vgg16.py:26-60, mobilenet_v1.py:114-172) ---------------------------------------------------- */
 /* Implicit-GEMM convolution on the f32 MFMA pipe (v_mfma_f32_32x32x2_f32).

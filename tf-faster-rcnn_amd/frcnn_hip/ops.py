@@ -243,6 +243,37 @@ def bbox_overlaps(boxes, query):
     return out
 
 
+def coco_match(det_xywh, det_off, gt_xywh, gt_area, gt_crowd, gt_off, iou_thrs, area_rng, want_iou=False):
+    """COCO bbox matching of every (image, category) group (frcnn_coco_match): device tensors det_xywh [n_det,4] f64 (per group sorted
+    by -score, cut to max_det), gt_xywh [n_gt,4] f64, gt_area [n_gt] f64, gt_crowd [n_gt] u8, iou_thrs [T] f64, area_rng [A,2] f64; the CSR
+    offsets det_off / gt_off [n_groups+1] are HOST int64 arrays: they are checked against the tensors here (non-decreasing from 0, totals
+    = n_det / n_gt), the pair total and the workspace size follow from them, and they are uploaded for the kernel -- so no caller can
+    hand the entry a workspace sized for other totals.  Returns (det_matched [A,T,n_det] u8, det_ignored [A,T,n_det] u8, gt_ignored
+    [A,n_gt] u8, iou [n_pairs] f64 or None) on the current stream, zero where no group covers an element."""
+    for t, dt in ((det_xywh, torch.float64), (gt_xywh, torch.float64), (gt_area, torch.float64), (iou_thrs, torch.float64),
+                  (area_rng, torch.float64), (gt_crowd, torch.uint8)):
+        _chk(t, dt)
+    det_off, gt_off = (np.ascontiguousarray(o, dtype=np.int64).reshape(-1) for o in (det_off, gt_off))
+    n_groups, n_det, n_gt, T, A = det_off.size - 1, det_xywh.shape[0], gt_xywh.shape[0], iou_thrs.numel(), area_rng.shape[0]
+    if n_groups < 0 or gt_off.size != n_groups + 1 or gt_area.numel() != n_gt or gt_crowd.numel() != n_gt or area_rng.numel() != 2 * A:
+        raise ValueError("coco_match: inconsistent sizes")
+    for off, total in ((det_off, n_det), (gt_off, n_gt)):
+        if off[0] != 0 or off[-1] != total or np.any(np.diff(off) < 0):
+            raise ValueError("coco_match: offsets must run from 0 to the number of rows without decreasing")
+    n_pairs = int(np.sum(np.diff(det_off) * np.diff(gt_off)))
+    dev = det_xywh.device
+    det_off_d, gt_off_d = torch.from_numpy(det_off).to(dev), torch.from_numpy(gt_off).to(dev)
+    matched = _zeros((A, T, n_det), dtype=torch.uint8, device=dev)
+    ignored = _zeros((A, T, n_det), dtype=torch.uint8, device=dev)
+    gt_ignored = _zeros((A, n_gt), dtype=torch.uint8, device=dev)
+    iou = _empty((n_pairs,), dtype=torch.float64, device=dev) if want_iou else None
+    nbytes = lib().frcnn_coco_match_workspace_bytes(n_groups, n_det, n_gt, n_pairs)
+    ws = workspace(nbytes, dev, "coco_match")
+    call("frcnn_coco_match", _ptr(det_xywh), _ptr(det_off_d), _ptr(gt_xywh), _ptr(gt_area), _ptr(gt_crowd), _ptr(gt_off_d), n_groups,
+         _ptr(iou_thrs), T, _ptr(area_rng), A, _ptr(matched), _ptr(ignored), _ptr(gt_ignored), _ptr(iou), _ptr(ws), nbytes, _stream())
+    return matched, ignored, gt_ignored, iou
+
+
 def bbox_transform_inv(boxes, deltas, out=None):
     """lib/model/bbox_transform.py:35-65 on device: boxes [N,4], deltas [N,4k] -> [N,4k]."""
     _chk(boxes), _chk(deltas)

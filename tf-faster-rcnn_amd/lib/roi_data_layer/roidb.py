@@ -1,16 +1,21 @@
-"""roi_data_layer.roidb -- prepare_roidb of the reference (lib/roi_data_layer/roidb.py:19-49): image path, size (PIL), and the per-box
-maximum overlap / class derived from gt_overlaps, added to every roidb entry in place."""
+"""roi_data_layer.roidb -- prepare_roidb of the reference (lib/roi_data_layer/roidb.py:19-49): image path, size, and the per-box maximum
+overlap / class derived from gt_overlaps, added to every roidb entry in place.  The size comes from PIL, except for an imdb whose name
+starts with `coco` (roidb.py:27-34): its entries already carry width / height from the annotation file, and opening 80 000 images
+to read two numbers is not free."""
 import numpy as np
 import PIL.Image
 
 
 def prepare_roidb(imdb):
     roidb = imdb.roidb
-    sizes = [PIL.Image.open(imdb.image_path_at(i)).size for i in range(imdb.num_images)]
+    from_entries = imdb.name.startswith('coco')
+    if not from_entries:
+        sizes = [PIL.Image.open(imdb.image_path_at(i)).size for i in range(imdb.num_images)]
     for i in range(len(imdb.image_index)):
         roidb[i]['image'] = imdb.image_path_at(i)
-        roidb[i]['width'] = sizes[i][0]
-        roidb[i]['height'] = sizes[i][1]
+        if not from_entries:
+            roidb[i]['width'] = sizes[i][0]
+            roidb[i]['height'] = sizes[i][1]
         gt_overlaps = roidb[i]['gt_overlaps'].toarray()            # dense for argmax
         max_overlaps = gt_overlaps.max(axis=1)
         max_classes = gt_overlaps.argmax(axis=1)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Train a Faster R-CNN network on the MI355X path -- entry point of the reference's tools/trainval_net.py:29-139
 with the same flags (--cfg --weight --imdb --imdbval --iters --tag --net --set).  `--imdb voc_2007_trainval` (or `a+b`) trains
-on the roidb of `<cfg.DATA_DIR>/VOCdevkit<year>` through roi_data_layer.layer.RoIDataLayer: flipped twins iff cfg.TRAIN.USE_FLIPPED,
+on the roidb of `<cfg.DATA_DIR>/VOCdevkit<year>`, `--imdb coco_2014_train` on that of `<cfg.DATA_DIR>/coco` (81 classes; crowd boxes are no
+foreground), through roi_data_layer.layer.RoIDataLayer: flipped twins iff cfg.TRAIN.USE_FLIPPED,
 snapshots under get_output_dir(imdb, tag) unless --output names another directory; `--imdb synthetic` (default) feeds seeded synthetic
 images + gt boxes and writes snapshots only with --output.  --imdbval is accepted and unused (the reference reads it for TensorBoard
 summaries only).  Multi-GPU: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/trainval_net.py ...` (one
@@ -28,7 +29,7 @@ def parse_args():
     parser.add_argument('--cfg', dest='cfg_file', help='optional config file', default=None, type=str)
     parser.add_argument('--weight', dest='weight', help='initialize with pretrained model weights (TF V2 checkpoint prefix, or .npz)', type=str)
     parser.add_argument('--output', dest='output_dir', help='directory for snapshots (default: output/<EXP_DIR>/<imdb>/<tag> for a dataset, none for synthetic)', default=None, type=str)
-    parser.add_argument('--imdb', dest='imdb_name', help='dataset to train on: synthetic | voc_<year>_<split>[+...]', default='synthetic', type=str)
+    parser.add_argument('--imdb', dest='imdb_name', help='dataset to train on: synthetic | voc_<year>_<split> | coco_<year>_<set> [+...]', default='synthetic', type=str)
     parser.add_argument('--imdbval', dest='imdbval_name', help='dataset to validate on', default='synthetic', type=str)
     parser.add_argument('--iters', dest='max_iters', help='number of iterations to train', default=70000, type=int)
     parser.add_argument('--tag', dest='tag', help='tag of the model', default=None, type=str)

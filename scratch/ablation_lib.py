@@ -1,5 +1,5 @@
-"""Measurement builds: libfrcnn_hip.so with -DFRCNN_ABLATION (the extra frcnn_gemm_h2 / frcnn_gemm_x3 configurations the sweeps
-compare; some give wrong results by construction) into /tmp, and frcnn_hip bound to it.  Import BEFORE frcnn_hip:
+"""Measurement builds: libfrcnn_hip.so with -DFRCNN_ABLATION (the energy ledger's frcnn_gemm_h2 configurations 50-55: wrong results
+by construction) and / or other -D flags, into /tmp, and frcnn_hip bound to it.  Import BEFORE frcnn_hip:
 
     import ablation_lib; ablation_lib.use()
 """

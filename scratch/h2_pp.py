@@ -1,9 +1,7 @@
-"""frcnn_gemm_h2: the one-barrier-per-slab schedule (cfg 9 = shipped in round 3, cfg 3 = its 256 x 128 / 8-wave form) against the
-ping-pong schedule (cfg 21) on the GEMM shapes of the path: time (interleaved A/B in one process), f32-equivalent TFLOP/s, bit equality."""
+"""frcnn_gemm_h2: the one-barrier-per-slab schedule (cfg 9 = shipped in round 3) against the ping-pong schedule (cfg 21) on the GEMM
+shapes of the path: time (interleaved A/B in one process), f32-equivalent TFLOP/s, bit equality."""
 import sys, os
 sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tf-faster-rcnn_amd")]
-sys.path[:0] = [os.path.dirname(os.path.abspath(__file__))]
-import ablation_lib; ablation_lib.use()
 import numpy as np, torch
 from frcnn_hip import ops
 dev = torch.device("cuda:0")
@@ -16,7 +14,7 @@ shapes = {  # name: (G, M, N, K, residual, planes out)
  "b3c1x1": (1, 2394, 256, 1024, False, True), "b3c3x1": (1, 2394, 1024, 256, True, True), "w3x1": (36, 160, 256, 256, False, False),
  "b2c1x4": (1, 37500, 128, 512, False, True), "b2c3x4": (1, 37500, 512, 128, True, True), "b3scx4": (1, 9576, 1024, 512, False, True),
 }
-cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "9,3,21").split(",")]
+cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "9,21").split(",")]
 only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(shapes)
 print("%-8s %-4s %9s %9s %8s  %s" % ("shape", "cfg", "med_us", "min_us", "TFLOP/s", "bits vs cfg %d" % cfgs[0]))
 for name in only:

@@ -277,7 +277,7 @@ def test_gemm_h2_ping_pong_is_bit_identical_to_the_one_barrier_schedule(dev, sha
                                    (1, 100, 128, 128), (2, 128, 128, 384)],
                          ids=["b4c3", "b3c3", "b2c3_four_slabs_per_tile", "batched_tails", "one_partial_tile", "one_tile_per_entry"])
 def test_gemm_h2_deferred_epilogue_every_form_is_bit_identical(dev, shape, form):
-    """The deferred epilogue (cfgs 40 / 41, csrc/gemm_h2.hip "TUNE & 1024") in the forms the network launches -- the SHIPPED one first:
+    """The deferred epilogue (cfgs 40 / 41, csrc/gemm_h2.hip "H2_DEFERRED") in the forms the network launches -- the SHIPPED one first:
     residual read as operand planes, planes only out (the identity units of a trunk kept as planes) -- against cfg 9 on the same
     operands: same f32 bits, same plane bits, same block scales, six launches each.  Covers K = 128 (a tile is exactly the four slabs
     the drain needs), one tile per workgroup (nothing to defer: the standalone epilogue alone), M tails inside batch entries (rows past

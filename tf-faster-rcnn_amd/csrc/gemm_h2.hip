@@ -53,9 +53,6 @@ struct GemmH2Params {
   int wshare;                         // 1: every batch entry multiplies by W[0] (frcnn_gemm_h2_mean: entries = images); 0: entry g by W[g]
   const float* mask;                  // frcnn_gemm_h2_masked (training): result = mask > 0 ? result : 0, mask [batch * M][N] float32
   float* mean_part; int mean_rows;    // frcnn_gemm_h2_mean: the result is not stored; column sums of row groups go to mean_part [batch][ceil(M / 32)][2][N]
-#ifdef FRCNN_H2_TRACE
-  unsigned long long* trace;          // measurement builds only (scratch/h2_trace.py): s_memtime stamps of the first slabs of a few workgroups
-#endif
 };
 
 // one direct-to-LDS load: 64 lanes x 16 B from (scalar base + per-lane 32-bit byte offset) to LDS [lds_base, +1 KiB), lane-linear.
@@ -114,8 +111,38 @@ __device__ __forceinline__ void h2_wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// TUNE bits (A/B measurements, all produce identical results): 1 = the slab's loads are issued in two halves around the first k group
-// instead of in one burst after the barrier; 2 = the block scales travel only with the first slab of a 128-k block (NS == 2 only)
+// TUNE: a mask of the bits below.  Every combination the dispatch table (h2_dispatch) instantiates multiplies and folds in the same
+// order and gives bit-identical results; the bits choose schedule and epilogue form only.
+enum H2Tune : int {
+  H2_SCALES_ONCE = 2,        // the block scales travel only with the first slab of a 128-k block (two-slot ring or ping-pong)
+  H2_PINGPONG = 32,          // the ping-pong schedule: 8 waves in two groups, one barrier apart, 3-slot ring
+  H2_MASKED = 128,           // frcnn_gemm_h2_masked: the ReLU-gradient select in the epilogue (the training instantiations)
+  H2_LIGHT_BOUNDARY = 256,   // the light tile boundary (round 5): no dependent memory round trip, no store drain between tiles
+  H2_STORE16 = 512,          // plane stores widened to 16 B per lane by v_permlane32_swap pairs (half the instructions)
+  H2_DEFERRED = 1024,        // the deferred epilogue (round 6): tile t drains under the first 128-k block of tile t + 1
+#ifdef FRCNN_ABLATION
+  // the energy ledger (scratch/energy_ledger.py; wrong results by construction): one ingredient of the slab loop taken out
+  H2_NO_MFMA = 2048,         // no MFMAs (the fragments are still read)
+  H2_NO_FRAG = 4096,         // no fragment reads (the MFMAs run on whatever the registers hold)
+  H2_NO_LOAD = 8192,         // no slab loads after the prologue (the ring is never refilled)
+#endif
+};
+
+// The dynamic LDS of one workgroup, in bytes from its start: the kernel addresses it by these offsets, launch_h2 requests TOTAL.
+template <int BM, int BN, int WM, int WN, int NS, int TUNE>
+struct H2Lds {
+  static constexpr int NW = (BM / WM) * (BN / WN);
+  static constexpr bool PP = (TUNE & H2_PINGPONG) != 0;
+  static constexpr int XP = BM * 64, WP = BN * 64;          // one plane of a stage
+  static constexpr int S_OFF = 2 * XP + 2 * WP;             // inside a stage: the BM block scales (1 KB; not with PP)
+  static constexpr int STAGE = S_OFF + (PP ? 0 : 1024);
+  static constexpr int RED_OFF = NS * STAGE;                // row-maximum exchange of the plane-emitting epilogue: [BN / WN][BM] floats
+  static constexpr int S2_OFF = RED_OFF + (BN / WN) * BM * 4;      // H2_SCALES_ONCE: two 1 KB block-scale regions, alternating per 128-k block
+                                                                   // PP: [wave][parity] 256 B: each wave's own 64 row scales
+  static constexpr int CB_OFF = S2_OFF + (PP ? NW * 512 : (TUNE & H2_SCALES_ONCE) ? 2048 : 0);   // H2_LIGHT_BOUNDARY: [tile parity][filter scales BN | bias BN] floats
+  static constexpr int TOTAL = CB_OFF + ((TUNE & H2_LIGHT_BOUNDARY) ? 2 * 2 * BN * 4 : 0);
+};
+
 template <int BM, int BN, int WM, int WN, int NS, int WPE = 2, int TUNE = 0>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_gemm_h2(const GemmH2Params p) {
   constexpr int NW = (BM / WM) * (BN / WN);
@@ -124,20 +151,17 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   constexpr int LB = 2 * BN / 16 / NW;            // W planes
   constexpr int G = LA + LB;                      // per wave per slab (wave 0 issues SL more: the block scales, 64 rows each)
   constexpr int SL = BM / 64;
-  constexpr int XP = BM * 64, WP = BN * 64;       // bytes of one plane of a stage
-  constexpr bool PP = (TUNE & 32) != 0;           // the ping-pong schedule (below): 8 waves in two groups, one barrier apart
-  constexpr bool LTB = (TUNE & 256) != 0;         // the light tile boundary (round 5, below): no dependent memory round trip, no store drain
-  constexpr bool W21 = (TUNE & 512) != 0;         // plane stores widened to 16 B per lane by v_permlane32_swap pairs (half the instructions)
-  constexpr bool DE = (TUNE & 1024) != 0;         // the deferred epilogue (round 6, below): tile t drains under the first 128-k block of tile t + 1
-  constexpr int NTA = (TUNE & 16384) ? 2 : 0;     // `nt` on the streams a tile touches once (residual loads, result stores): cache-policy experiment (cfg 42)
-  constexpr int S_OFF = 2 * XP + 2 * WP, STAGE = S_OFF + (PP ? 0 : 1024);
-  constexpr int RED_OFF = NS * STAGE;             // row-maximum exchange of the plane-emitting epilogue: [BN / WN][BM] floats
-  constexpr int S2_OFF = RED_OFF + (BN / WN) * BM * 4;      // TUNE & 2: two 1 KB block-scale regions, alternating per 128-k block
-                                                            // PP: [wave][parity] 256 B: each wave's own 64 row scales
-  constexpr int CB_OFF = S2_OFF + (PP ? NW * 512 : (TUNE & 2) ? 2048 : 0);   // LTB: [tile parity][filter scales BN | bias BN] floats
+  constexpr bool ONCE = (TUNE & H2_SCALES_ONCE) != 0;
+  constexpr bool PP = (TUNE & H2_PINGPONG) != 0;
+  constexpr bool MASKED = (TUNE & H2_MASKED) != 0;
+  constexpr bool LTB = (TUNE & H2_LIGHT_BOUNDARY) != 0;
+  constexpr bool W21 = (TUNE & H2_STORE16) != 0;
+  constexpr bool DE = (TUNE & H2_DEFERRED) != 0;
+  using L = H2Lds<BM, BN, WM, WN, NS, TUNE>;
+  constexpr int XP = L::XP, WP = L::WP, S_OFF = L::S_OFF, STAGE = L::STAGE, RED_OFF = L::RED_OFF, S2_OFF = L::S2_OFF, CB_OFF = L::CB_OFF;
   static_assert(!LTB || (!PP && NS == 2 && NW >= 3 && BN % 64 == 0), "light boundary: the two-slot one-barrier-per-slab schedule");
   static_assert(!DE || (LTB && W21 && BN == H2_KB), "deferred epilogue: built on the light boundary's LDS constants and counted waits");
-  static_assert(!PP || (NW == 8 && NS == 3 && (TUNE & 2) && ((BM == 256 && WM == 64) || (BM == 128 && WM == 32)) && BN == 128 && WN == 64),
+  static_assert(!PP || (NW == 8 && NS == 3 && ONCE && BM == 256 && WM == 64 && BN == 128 && WN == 64),
                 "ping-pong geometry: 8 waves as 4 (M) x 2 (N), waves 0-3 = the upper half of the rows");
   static_assert((2 * BM / 16) % NW == 0 && (2 * BN / 16) % NW == 0, "tile/wave mismatch");
   static_assert(BM <= 256 && NS >= 2 && NS <= 4, "stage layout");
@@ -169,28 +193,12 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
 #pragma unroll
   for (int t = 0; t < LB; ++t) {
     const int u = wave * LB + t, plane = u / (BN / 16), row = (u % (BN / 16)) * 16 + (lane >> 2), pos = lane & 3;
-    b_off[t] = (unsigned)((size_t)plane * wplane + (size_t)row * p.K * 2 + ((pos ^ ((row >> ((TUNE & 8) ? 1 : 2)) & 3)) * 16));
-#ifdef FRCNN_ABLATION     // TUNE & 16: the same bytes as 8 rows x one full 128-byte line per instruction (timing only: wrong LDS image)
-    if (TUNE & 16) b_off[t] = (unsigned)((size_t)(u * 8 + (lane >> 3)) * p.K * 2 + (lane & 7) * 16);
-#endif
+    b_off[t] = (unsigned)((size_t)plane * wplane + (size_t)row * p.K * 2 + ((pos ^ ((row >> 2) & 3)) * 16));
   }
-  // tile id -> (batch entry, row tile, column tile).  TUNE & 32768 (experiment, cfg 43): inside a batch entry the ids walk PANELS of 8 row
-  // tiles x 8 column tiles, the column groups of odd panels in reverse -- the 64 tiles an XCD has resident then touch 2 + 2 MB of operands
-  // per round (K = 512) instead of 1 + 4 MB in the row-major order (the filter planes re-fetched every round, profiles/r06_counters_conv3.json)
-  constexpr bool PANEL = (TUNE & 32768) != 0;
+  // tile id -> (batch entry, row tile, column tile), row-major inside a batch entry
   auto tile_coords = [&](int tl, int& g, int& mt, int& nt) {
     g = tl / per;
     const int rem = tl - g * per;
-    if (PANEL && (p.ntiles & 7) == 0) {
-      const int per_panel = 8 * p.ntiles, panel = rem / per_panel, r2 = rem - panel * per_panel;
-      const int pm = min(8, p.mtiles - panel * 8), per_grp = pm * 8;
-      int grp = r2 / per_grp;
-      const int r3 = r2 - grp * per_grp;
-      if (panel & 1) grp = (p.ntiles >> 3) - 1 - grp;
-      mt = panel * 8 + (r3 >> 3);
-      nt = grp * 8 + (r3 & 7);
-      return;
-    }
     mt = rem / p.ntiles;
     nt = rem - mt * p.ntiles;
   };
@@ -201,19 +209,13 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     const size_t row0 = (size_t)g * p.M + bm0;
     i_g = g; i_bn0 = bn0;
     i_xb = (const char*)p.x + row0 * p.K * 2;
-#ifdef FRCNN_ABLATION     // TUNE & 64: every tile reads the FIRST tile's X rows (cache-resident operands: what does the HBM latency cost?)
-    if (TUNE & 64) i_xb = (const char*)p.x;
-#endif
     i_wb = (const char*)p.w + ((size_t)(p.wshare ? 0 : g) * 2 * p.N + bn0) * p.K * 2;
     i_sb = (const char*)(p.x_inv + row0);
 #pragma unroll
     for (int t = 0; t < LA; ++t) {
       const int u = wave * LA + t, plane = u / (BM / 16), row = (u % (BM / 16)) * 16 + (lane >> 2), pos = lane & 3;
       const int rr = min(row, p.M - 1 - bm0);                                           // rows past M re-read row M - 1
-      a_off[t] = (unsigned)((size_t)plane * xplane + (size_t)rr * p.K * 2 + ((pos ^ ((row >> ((TUNE & 8) ? 1 : 2)) & 3)) * 16));
-#ifdef FRCNN_ABLATION
-      if (TUNE & 16) a_off[t] = (unsigned)((size_t)min(u * 8 + (lane >> 3), p.M - 1 - bm0) * p.K * 2 + (lane & 7) * 16);
-#endif
+      a_off[t] = (unsigned)((size_t)plane * xplane + (size_t)rr * p.K * 2 + ((pos ^ ((row >> 2) & 3)) * 16));
     }
     // block scales of the tile's rows: one float per lane and 64-row group; rows past the tensor re-read its last row (unused)
     const long long last = p.Mtot - 1 - (long long)row0;
@@ -241,25 +243,20 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     else if (t < G) h2_glds16(b_off[t - LA], uniform_ptr(i_wb), __builtin_amdgcn_readfirstlane(sb + 2 * XP + (wave * LB + (t - LA)) * 1024));
     else if (wave == 0) {
       const int j = t - G;
-      if (!(TUNE & 2)) h2_glds4(s_off[j], uniform_ptr(i_sb), __builtin_amdgcn_readfirstlane(sb + S_OFF + j * 256));
+      if (!ONCE) h2_glds4(s_off[j], uniform_ptr(i_sb), __builtin_amdgcn_readfirstlane(sb + S_OFF + j * 256));
       else if ((i_step & 3) == 0) {              // once per 128-k block, into the parity region of that block (not a ring slot)
         h2_glds4(s_off[j], uniform_ptr(i_sb), __builtin_amdgcn_readfirstlane(lds0 + S2_OFF + i_par * 1024 + j * 256));
         if (j == SL - 1) i_par ^= 1;
       }
     }
   };
-  static_assert(!(TUNE & 2) || NS == 2 || PP, "scales-once needs the uncounted wait of the two-stage ring");
+  static_assert(!ONCE || NS == 2 || PP, "scales-once needs the uncounted wait of the two-stage ring");
   auto issue_advance = [&]() {                      // after the last piece of a slab
     --left;
     if (++i_step == p.nsteps) {
       i_step = 0; i_tile += W8;
       if (left > 0) set_tile(i_tile);
     } else {
-#ifdef FRCNN_ABLATION
-      if (TUNE & 16) {          // line s of plane (s & 1): every 128-byte line of both planes is fetched exactly once
-        if (i_step & 1) { i_xb += xplane - 64; i_wb += wplane - 64; } else { i_xb += 128 - xplane - 64; i_wb += 128 - wplane - 64; }
-      }
-#endif
       i_xb += 64; i_wb += 64;
       if ((i_step & 3) == 0) i_sb += (size_t)p.Mtot * 4;       // next 128-k block: next row of x_inv [K/128][Mtot]
     }
@@ -306,29 +303,21 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
 
   // ---- compute side -------------------------------------------------------------------------------------------------------------
   f32x16 tot[TM][TN], tmp[TM][TN];
-  const int sw = (frow >> ((TUNE & 8) ? 1 : 2)) & 3;        // TUNE & 8: round-2 swizzle (two-way bank conflicts), kept for A/B runs
+  const int sw = (frow >> 2) & 3;
   const int x_row = (wm0 + frow) * 64, w_row = 2 * XP + (wn0 + frow) * 64;
 
-  // TUNE & 4: the next slab's G + SL direct-to-LDS loads are issued ONE AT A TIME between the MFMAs of the current slab (evenly spread
-  // over its NM MFMAs, the first after MFMA 1) instead of in a burst after the barrier: a load's issue stall (~60-150 cycles) then falls
-  // under the matrix-pipe time of the MFMAs already issued, not in front of the slab's first fragment reads.
-  constexpr int NM = 2 * 3 * TM * TN, ND = G + SL;
-  // FRCNN_ABLATION builds (the energy ledger, scratch/energy_ledger.py; wrong results by construction): TUNE & 2048 = no MFMAs (the
-  // fragments are still read), TUNE & 4096 = no fragment reads (the MFMAs run on whatever the registers hold), TUNE & 8192 = no slab
-  // loads after the prologue (the ring is never refilled)
-#ifdef FRCNN_ABLATION
-  constexpr bool NO_MFMA = (TUNE & 2048) != 0, NO_FRAG = (TUNE & 4096) != 0, NO_LOAD = (TUNE & 8192) != 0;
+#ifdef FRCNN_ABLATION     // the energy ledger (H2Tune)
+  constexpr bool NO_MFMA = (TUNE & H2_NO_MFMA) != 0, NO_FRAG = (TUNE & H2_NO_FRAG) != 0, NO_LOAD = (TUNE & H2_NO_LOAD) != 0;
 #else
   constexpr bool NO_MFMA = false, NO_FRAG = false, NO_LOAD = false;
 #endif
   h8 kxh[NO_FRAG ? TM : 1], kxl[NO_FRAG ? TM : 1], kwh[NO_FRAG ? TN : 1], kwl[NO_FRAG ? TN : 1];     // (ablation: the kept fragments)
   (void)kxh; (void)kxl; (void)kwh; (void)kwl;
-  auto slab_mfma = [&](int cur, auto first_c, auto&& between, auto&& after) {
+  auto slab_mfma = [&](int cur, auto first_c) {
     constexpr bool FIRST = decltype(first_c)::value;
     const char* sb = smem + cur * STAGE;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {                    // two groups of 16 k per 32-wide slab
-      if (t == 1) between();
       h8 xh[TM], xl[TM], wh[TN], wl[TN];
       if constexpr (NO_FRAG) {          // (ablation) the first 16-k group of every 128-k block is read and serves the whole block: real operand
         if (FIRST && t == 0) {          // values (the matrix pipe's power follows its data), 1 / 8 of the LDS fragment reads
@@ -391,21 +380,18 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
           } else {
             tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[j], xh[i], tmp[i][j], 0, 0, 0);
           }
-          after(t * 3 * TM * TN + i * TN + j);
         }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[j], xh[i], tmp[i][j], 0, 0, 0);
-          after(t * 3 * TM * TN + TM * TN + i * TN + j);
         }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[j], xl[i], tmp[i][j], 0, 0, 0);
-          after(t * 3 * TM * TN + 2 * TM * TN + i * TN + j);
         }
     }
   };
@@ -444,22 +430,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     return __builtin_amdgcn_readfirstlane((T.bm0 + wm0 + i * 32) * p.N + T.bn0 + wn0 + j * 32);
   };
 
-#ifdef FRCNN_H2_TRACE
-  int tr_slab = 0;
-  auto stamp = [&](int point) {       // [workgroup < 16][wave][slab < 64][point < 8]
-    if (p.trace && blockIdx.x < 16 && tr_slab < 64 && lane == 0)
-      p.trace[(((size_t)blockIdx.x * NW + wave) * 64 + tr_slab) * 8 + point] = __builtin_amdgcn_s_memtime();
-  };
-  // tile-boundary stamps (scratch/h2_trace_boundary.py): a second region behind the slab stamps, [workgroup < 16][wave][tile < 32][point < 8]
-  int tr_tile = 0;
-  auto bstamp = [&](int point) {
-    if (p.trace && blockIdx.x < 16 && tr_tile < 32 && lane == 0)
-      p.trace[(size_t)16 * 8 * 64 * 8 + (((size_t)blockIdx.x * NW + wave) * 32 + tr_tile) * 8 + point] = __builtin_amdgcn_s_memtime();
-  };
-#else
-  auto stamp = [](int) {};
-  auto bstamp = [](int) {};
-#endif
   float rri[TM];                                                // DE: the residual planes' block scales of the tile's rows (raw residual: first fold)
   (void)rri;
   // The tile's residual (tile under the c_* cursor), sub-tile row i, RAW into tot[i][*]: always four 16-byte loads per sub-tile through ONE instruction stream --
@@ -483,7 +453,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
       const int vo = base + sub_off(C, i, j) * (planes ? 2 : 4);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128((q & 1) ? r_odd : r_even, vo, q * step_q + (q >> 1) * step_p, NTA);
+        const u32x4 ld = __builtin_amdgcn_raw_buffer_load_b128((q & 1) ? r_odd : r_even, vo, q * step_q + (q >> 1) * step_p, 0);
         tot[i][j][4 * q + 0] = __uint_as_float(ld[0]); tot[i][j][4 * q + 1] = __uint_as_float(ld[1]);
         tot[i][j][4 * q + 2] = __uint_as_float(ld[2]); tot[i][j][4 * q + 3] = __uint_as_float(ld[3]);
       }
@@ -616,9 +586,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     }
   };
   // frcnn_gemm_h2_masked: the ReLU gradient of the tensor this result is the gradient of (an exact select; NaN / inf of the result pass
-  // where the mask is positive, like frcnn_relu_bwd).  TUNE & 128: the training instantiations (the inference kernels do not carry this code)
+  // where the mask is positive, like frcnn_relu_bwd).  H2_MASKED: the training instantiations (the inference kernels do not carry this code)
   auto ep_mask = [&](const TileRef& T) {
-    if ((TUNE & 128) && p.mask) {
+    if (MASKED && p.mask) {
       const auto rk = ent_rsrc(p.mask, T.g, 4);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -697,7 +667,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         // (__float_as_uint, not __builtin_bit_cast: bit_cast of an ext-vector ELEMENT lvalue reads element 0 -- clang 19 / ROCm 7.2)
         o[0] = __float_as_uint(tot[i][j][4 * q + 0]); o[1] = __float_as_uint(tot[i][j][4 * q + 1]);
         o[2] = __float_as_uint(tot[i][j][4 * q + 2]); o[3] = __float_as_uint(tot[i][j][4 * q + 3]);
-        __builtin_amdgcn_raw_buffer_store_b128(o, ry, lo + 32 * q, 0, NTA);
+        __builtin_amdgcn_raw_buffer_store_b128(o, ry, lo + 32 * q, 0, 0);
       }
       pend += 4;
       if constexpr (DE) __builtin_amdgcn_sched_barrier(0);
@@ -756,8 +726,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
           typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
           const auto h0 = __builtin_amdgcn_permlane32_swap(uha[0], uhb[0], false, false), h1 = __builtin_amdgcn_permlane32_swap(uha[1], uhb[1], false, false);
           const auto l0 = __builtin_amdgcn_permlane32_swap(ula[0], ulb[0], false, false), l1 = __builtin_amdgcn_permlane32_swap(ula[1], ulb[1], false, false);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{h0[0], h1[0], h0[1], h1[1]}, rh, lo + 32 * pq, 0, NTA);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{l0[0], l1[0], l0[1], l1[1]}, rl, lo + 32 * pq, 0, NTA);
+          __builtin_amdgcn_raw_buffer_store_b128(u32x4{h0[0], h1[0], h0[1], h1[1]}, rh, lo + 32 * pq, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(u32x4{l0[0], l1[0], l0[1], l1[1]}, rl, lo + 32 * pq, 0, 0);
         }
         pend += 4;
         if constexpr (DE) __builtin_amdgcn_sched_barrier(0);        // (one sub-tile's split temporaries at a time: the pieces run beside 128 live accumulators)
@@ -778,9 +748,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   // the standalone epilogue of the tile under the c_* cursor: every part back to back, after the tile's last fold
   auto epilogue = [&]() {
     const TileRef T{c_bm0, c_bn0, c_g, c_cpar};
-    bstamp(0);
     ep_scale_act(T);
-    bstamp(1);
     ep_mask(T);
     if (p.mean_part) {
       ep_mean(T);
@@ -789,7 +757,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) ep_store_f32(T, i);
-    bstamp(2);
     if (p.yp) {
       float mx[TM];
       ep_rowmax_write(mx);
@@ -801,20 +768,17 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         __builtin_amdgcn_s_barrier();
         ep_rowmax_merge(mx);
       }
-      bstamp(3);
 #pragma unroll
       for (int i = 0; i < TM; ++i) ep_store_planes(T, i, mx[i]);
-      bstamp(4);
       if (BN / WN > 1) {                                                         // red[] is reused by the next tile
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
       }
     }
-    bstamp(5);
     c_cpar ^= 1;
   };
 
-  // ---- the deferred epilogue (TUNE & 1024, round 6) -----------------------------------------------------------------------------------
+  // ---- the deferred epilogue (H2_DEFERRED, round 6) -----------------------------------------------------------------------------------
   // The counters of the conv3-class launches (profiles/r05_counters_conv3.json: waves on s_waitcnt 0.50 of their cycles, matrix pipe busy
   // 0.28) say one workgroup's serial chain binds: K loop -> scale / row maxima / barrier / split / stores -> residual round trip -> K
   // loop.  A second accumulator set would let tile t + 1 multiply while tile t drains -- and the registers for it exist without a third
@@ -855,12 +819,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     }
   };
 
-  // one slab of the stream: wait for it, let the ring slot it frees be refilled (loads spread over nothing here: they are issued
-  // right after the barrier, G + SL instructions, and land under the 24 * TM * TN / 4 MFMAs of this slab and the next NS - 2)
+  // one slab of the stream: wait for it, let the ring slot it frees be refilled (the loads are issued in one burst right after the
+  // barrier, G + SL instructions, and land under the 24 * TM * TN / 4 MFMAs of this slab and the next NS - 2)
   auto slab = [&](auto pos_c, bool fold, bool first_block) {
     constexpr int POS = decltype(pos_c)::value;          // position inside the 128-k block: 0 .. 3 (0: the block's first MFMAs take C = 0)
     const std::integral_constant<bool, POS == 0> first_c{};
-    stamp(0);
     if constexpr (DE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (a drain piece's row maxima are in LDS before the barrier)
     if constexpr (LTB) {
       wait_pending(pend);                              // the slab's loads are older than the `pend` instructions that may stay in flight
@@ -869,21 +832,16 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     } else {
       h2_wait_vmcnt<0>();                              // tail of the stream: nothing more will be issued
     }
-    stamp(1);
     __builtin_amdgcn_s_barrier();
-    stamp(2);
     const bool more = left > 0;
-    constexpr int HALF = NO_LOAD ? 0 : (TUNE & 4) ? 0 : (TUNE & 1) ? (G + SL) / 2 : G + SL;
-    static_assert(!LTB || NO_LOAD || HALF == G + SL, "light boundary: the slab's loads are issued in one burst");
     if (more) {
 #pragma unroll
-      for (int t = 0; t < HALF; ++t) issue_one(nxt, t);
+      for (int t = 0; t < (NO_LOAD ? 0 : G + SL); ++t) issue_one(nxt, t);
       if constexpr (LTB) {
         if (i_step == 0) issue_cb();                   // first slab of a tile: its filter scales and bias travel with it
         pend = 0;
       }
     }
-    stamp(3);
     if constexpr (DE) {
       // (scheduling fences: the piece's temporaries die before the slab's fragments are read -- without them the scheduler interleaves the
       // two and the kernel spills)
@@ -893,29 +851,12 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     }
     float ainv[TM];
     if (fold) {
-      const int soff = (TUNE & 2) ? S2_OFF + c_par * 1024 : cur * STAGE + S_OFF;
+      const int soff = ONCE ? S2_OFF + c_par * 1024 : cur * STAGE + S_OFF;
 #pragma unroll
       for (int i = 0; i < TM; ++i) ainv[i] = *(const float*)(smem + soff + (wm0 + i * 32 + frow) * 4);
       c_par ^= 1;
     }
-    if (!(TUNE & 4)) {
-      slab_mfma(cur, first_c, [&]() {
-        stamp(4);
-        if (more && !NO_LOAD) {
-#pragma unroll
-          for (int t = HALF; t < G + SL; ++t) issue_one(nxt, t);
-        }
-      }, [](int) {});
-    } else if (more) {                                 // two code instances: the loads sit between the MFMAs without a branch each
-      slab_mfma(cur, first_c, []() {}, [&](int m) {
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-          if (1 + (d * (NM - 1)) / ND == m) issue_one(nxt, d);
-      });
-    } else {
-      slab_mfma(cur, first_c, []() {}, [](int) {});
-    }
-    stamp(5);
+    slab_mfma(cur, first_c);
     if (more) {
       issue_advance();
       nxt = nxt + 1 == NS ? 0 : nxt + 1;
@@ -977,10 +918,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
       }
     }
     cur = cur + 1 == NS ? 0 : cur + 1;
-    stamp(6);
-#ifdef FRCNN_H2_TRACE
-    ++tr_slab;
-#endif
   };
 
   set_tile(i_tile);
@@ -1023,7 +960,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     auto pp_mem = [&](auto pos_c, bool fold_prev) -> bool {
       constexpr int POS = decltype(pos_c)::value;
       const char* sb = smem + cur * STAGE;
-      stamp(0);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -1047,14 +983,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         nxt = nxt + 1 == NS ? 0 : nxt + 1;
       }
       if (fold_prev) fold();
-      stamp(1);
       if (grp == 1) {                        // slab q + 1 of THIS wave has landed (the slab q + 2 loads, G or G + 1 of them, stay in flight)
         if (more) h2_wait_vmcnt<(POS == 2 ? G + 1 : G)>(); else h2_wait_vmcnt<0>();
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(2);
       seg_barrier();
-      stamp(3);
       return more;
     };
     auto pp_mfma = [&](auto pos_c, bool issued) {
@@ -1085,17 +1018,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
           for (int j = 0; j < TN; ++j) tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxl[t][i], tmp[i][j], 0, 0, 0);
       }
       __builtin_amdgcn_s_setprio(0);
-      stamp(4);
       if (grp == 0) {
         if (issued) h2_wait_vmcnt<(POS == 2 ? G + 1 : G)>(); else h2_wait_vmcnt<0>();
       }
       cur = cur + 1 == NS ? 0 : cur + 1;
-      stamp(5);
       seg_barrier();
-      stamp(6);
-#ifdef FRCNN_H2_TRACE
-      ++tr_slab;
-#endif
     };
     // prologue: slabs 0 and 1 issued, slab 0 landed everywhere
     bool two = false;
@@ -1148,10 +1075,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   const int nkb = p.nsteps >> 2;
   for (int tl = 0; tl < my_tiles; ++tl) {
     init_tot();
-    bstamp(6);
-#ifdef FRCNN_H2_TRACE
-    ++tr_tile;                                         // (stamps 0-5 of tile t's epilogue and stamp 6 of tile t + 1's start share an index)
-#endif
     for (int kb = 0; kb < nkb; ++kb) {
       slab(std::integral_constant<int, 0>{}, false, kb == 0);
       slab(std::integral_constant<int, 1>{}, false, kb == 0);
@@ -1234,11 +1157,6 @@ __global__ __launch_bounds__(256) void k_h2_pack_w(const float* __restrict__ w, 
   if (l == 0) inv_out[row] = inv;
 }
 
-#ifdef FRCNN_H2_TRACE
-unsigned long long* g_h2_trace = nullptr;
-extern "C" void frcnn_h2_set_trace(unsigned long long* buf) { g_h2_trace = buf; }
-#endif
-
 extern "C" size_t frcnn_h2_planes_bytes(long long rows, int K) {
   if (rows <= 0 || K <= 0) return 0;
   return (size_t)2 * (size_t)rows * (size_t)K * sizeof(unsigned short);
@@ -1266,9 +1184,7 @@ extern "C" int frcnn_h2_split(const float* x_d, long long M, int K, void* planes
 template <int BM, int BN, int WM, int WN, int NS, int WPE = 2, int TUNE = 0>
 static int launch_h2(const GemmH2Params& q, hipStream_t st) {
   constexpr int NT = (BM / WM) * (BN / WN) * 64;
-  constexpr size_t lds = ((TUNE & 32) ? (size_t)NS * (2 * BM * 64 + 2 * BN * 64) + (size_t)(BN / WN) * BM * 4 + (size_t)(NT / 64) * 512
-                                      : (size_t)NS * (2 * BM * 64 + 2 * BN * 64 + 1024) + (size_t)(BN / WN) * BM * 4 + ((TUNE & 2) ? 2048 : 0)) +
-                         ((TUNE & 256) ? (size_t)2 * 2 * BN * 4 : 0);
+  constexpr size_t lds = H2Lds<BM, BN, WM, WN, NS, TUNE>::TOTAL;
   auto kern = k_gemm_h2<BM, BN, WM, WN, NS, WPE, TUNE>;
   static KernelOnce once;
   int slots = 0;                            // resident workgroups on the CURRENT device
@@ -1285,7 +1201,52 @@ static int launch_h2(const GemmH2Params& q, hipStream_t st) {
   return FRCNN_OK;
 }
 
+// The tile configurations, once: MASK = H2_MASKED gives every one its masked twin (frcnn_gemm_h2_masked: the data-gradient chain of the
+// training step takes the light tile boundary and the 16-byte plane stores by shape, like the forward pass), MASK = 0 the inference kernels.
+template <int MASK>
+static int h2_dispatch(const GemmH2Params& p, int cfg, hipStream_t st) {
+  switch (cfg) {
+    case 9: return launch_h2<128, 128, 64, 64, 2, 2, H2_SCALES_ONCE + MASK>(p, st);   // 67 KB: 2 workgroups / CU, one barrier per slab, scales once per 128-k block
+    case 12: return launch_h2<64, 128, 32, 64, 2, 2, MASK>(p, st);   // 64-row tiles, 4 waves of 32 x 64, 51 KB: 3 workgroups / CU (single-image launches)
+    case 21: return launch_h2<256, 128, 64, 64, 3, 2, H2_SCALES_ONCE + H2_PINGPONG + MASK>(p, st);   // ping-pong: 256 x 128, 8 waves in two groups a segment apart, 3-slot ring
+    case 30: return launch_h2<128, 128, 64, 64, 2, 2, H2_SCALES_ONCE + H2_LIGHT_BOUNDARY + MASK>(p, st);   // cfg 9 with the light tile boundary
+    case 31: return launch_h2<128, 128, 64, 64, 2, 2, H2_SCALES_ONCE + H2_LIGHT_BOUNDARY + H2_STORE16 + MASK>(p, st);   // ... and 16-byte plane stores
+    case 32: return launch_h2<128, 128, 64, 64, 2, 2, H2_SCALES_ONCE + H2_STORE16 + MASK>(p, st);   // cfg 9 with 16-byte plane stores only
+    case 33: return launch_h2<64, 128, 32, 64, 2, 2, H2_LIGHT_BOUNDARY + H2_STORE16 + MASK>(p, st);   // cfg 12 with both
+    case 34: return launch_h2<256, 128, 64, 64, 3, 2, H2_SCALES_ONCE + H2_PINGPONG + H2_STORE16 + MASK>(p, st);   // cfg 21 (ping-pong) with 16-byte plane stores
+    case 40: return launch_h2<128, 128, 64, 64, 2, 2, H2_SCALES_ONCE + H2_LIGHT_BOUNDARY + H2_STORE16 + H2_DEFERRED + MASK>(p, st);   // cfg 31 with the deferred epilogue (round 6)
+    case 41: return launch_h2<64, 128, 32, 64, 2, 2, H2_LIGHT_BOUNDARY + H2_STORE16 + H2_DEFERRED + MASK>(p, st);   // cfg 33 with the deferred epilogue
+  }
+#ifdef FRCNN_ABLATION
+  // the energy ledger (scratch/energy_ledger.py, measurement builds only): cfg 31 with one ingredient of the slab loop taken out
+  // (wrong results by construction)
+  constexpr int CFG31 = H2_SCALES_ONCE + H2_LIGHT_BOUNDARY + H2_STORE16;
+  if constexpr (MASK == 0) switch (cfg) {
+    case 50: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_MFMA>(p, st);   // no MFMAs
+    case 51: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_FRAG>(p, st);   // no fragment reads (LDS -> registers)
+    case 52: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_LOAD>(p, st);   // no slab loads (L2 -> LDS) after the prologue
+    case 53: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_MFMA + H2_NO_FRAG>(p, st);   // loads + epilogue only
+    case 54: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_FRAG + H2_NO_LOAD>(p, st);   // MFMAs + epilogue only
+    case 55: return launch_h2<128, 128, 64, 64, 2, 2, CFG31 + H2_NO_MFMA + H2_NO_FRAG + H2_NO_LOAD>(p, st);   // the epilogue (and the loop skeleton) only
+  }
+#endif
+  return FRCNN_E_ARG;
+}
+
 static int run_h2(GemmH2Params& p, int cfg, hipStream_t st);
+
+// the fields the three entry points share; each entry then sets its own form (mask / mean_part, mean_rows, wshare)
+static GemmH2Params h2_params(const void* x_planes_d, const float* x_inv_d, const void* w_planes_d, const float* w_inv_d, const float* bias_d,
+                              const float* res_d, const void* res_planes_d, const float* res_inv_d, float* y_d, void* y_planes_d, float* y_inv_d,
+                              int G, int M, int N, int K, int act) {
+  GemmH2Params p;
+  p.x = (const unsigned short*)x_planes_d; p.x_inv = x_inv_d; p.w = (const unsigned short*)w_planes_d; p.w_inv = w_inv_d;
+  p.bias = bias_d; p.res = res_d; p.resp = (const unsigned short*)res_planes_d; p.resp_inv = res_inv_d; p.y = y_d; p.yp = (unsigned short*)y_planes_d; p.y_inv = y_inv_d;
+  p.M = M; p.N = N; p.K = K; p.batch = G; p.act = act; p.Mtot = (long long)G * M;
+  p.nsteps = p.mtiles = p.ntiles = 0;
+  p.mean_part = nullptr; p.mean_rows = 0; p.wshare = 0; p.mask = nullptr;
+  return p;
+}
 
 // y[g] = act(x[g] W[g]^T + bias + res[g]), g < G.  x: planes [2][G*M][K] + x_inv [K/128][G*M] (frcnn_h2_split or a producer's `yp`
 // output); W: frcnn_h2_pack_w(W [G][N][K]); res / y [G*M][N] f32 (y may be null when only planes are wanted); the residual may be
@@ -1303,15 +1264,7 @@ extern "C" int frcnn_gemm_h2(const void* x_planes_d, const float* x_inv_d, const
   if (K % H2_KB || N % 128 || 4ll * Mtot * K >= (1ll << 32) || 4ll * N * K >= (1ll << 32) ||
       (long long)M * N >= (1ll << 29))
     return FRCNN_E_UNSUPPORTED;
-  GemmH2Params p;
-  p.x = (const unsigned short*)x_planes_d; p.x_inv = x_inv_d; p.w = (const unsigned short*)w_planes_d; p.w_inv = w_inv_d;
-  p.bias = bias_d; p.res = res_d; p.resp = (const unsigned short*)res_planes_d; p.resp_inv = res_inv_d; p.y = y_d; p.yp = (unsigned short*)y_planes_d; p.y_inv = y_inv_d;
-  p.M = M; p.N = N; p.K = K; p.batch = G; p.act = act; p.Mtot = Mtot;
-  p.nsteps = p.mtiles = p.ntiles = 0;
-#ifdef FRCNN_H2_TRACE
-  p.trace = g_h2_trace;
-#endif
-  p.mean_part = nullptr; p.mean_rows = 0; p.wshare = 0; p.mask = nullptr;
+  GemmH2Params p = h2_params(x_planes_d, x_inv_d, w_planes_d, w_inv_d, bias_d, res_d, res_planes_d, res_inv_d, y_d, y_planes_d, y_inv_d, G, M, N, K, act);
   return run_h2(p, cfg, (hipStream_t)stream);
 }
 
@@ -1327,15 +1280,8 @@ extern "C" int frcnn_gemm_h2_masked(const void* x_planes_d, const float* x_inv_d
     return FRCNN_E_ARG;
   const long long Mtot = (long long)G * M;
   if (K % H2_KB || N % 128 || 4ll * Mtot * K >= (1ll << 32) || 4ll * N * K >= (1ll << 32) || (long long)M * N >= (1ll << 29)) return FRCNN_E_UNSUPPORTED;
-  GemmH2Params p;
-  p.x = (const unsigned short*)x_planes_d; p.x_inv = x_inv_d; p.w = (const unsigned short*)w_planes_d; p.w_inv = w_inv_d;
-  p.bias = bias_d; p.res = res_d; p.resp = nullptr; p.resp_inv = nullptr; p.y = y_d; p.yp = (unsigned short*)y_planes_d; p.y_inv = y_inv_d;
-  p.M = M; p.N = N; p.K = K; p.batch = G; p.act = act; p.Mtot = Mtot;
-  p.nsteps = p.mtiles = p.ntiles = 0;
-#ifdef FRCNN_H2_TRACE
-  p.trace = g_h2_trace;
-#endif
-  p.mean_part = nullptr; p.mean_rows = 0; p.wshare = 0; p.mask = mask_d;
+  GemmH2Params p = h2_params(x_planes_d, x_inv_d, w_planes_d, w_inv_d, bias_d, res_d, nullptr, nullptr, y_d, y_planes_d, y_inv_d, G, M, N, K, act);
+  p.mask = mask_d;
   return run_h2(p, cfg, (hipStream_t)stream);
 }
 
@@ -1371,62 +1317,7 @@ static int run_h2(GemmH2Params& p, int cfg, hipStream_t st) {
     cfg = pp ? pp_cfg : tiny ? (cfg == -2 ? 12 : (de && cfg == -8) ? 41 : 33) : (cfg == -2 ? 9 : de ? 40 : 31);
   }
   if (p.mean_part && (cfg == 40 || cfg == 41)) cfg = cfg == 40 ? 31 : 33;     // (the fused-mean form keeps the standalone epilogue: same tiles)
-  if (p.mask) switch (cfg) {            // frcnn_gemm_h2_masked (TUNE & 128: the ReLU-gradient select in the epilogue): every shipped
-    case 9: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 128>(p, st);           // configuration has its masked twin since round 6 -- the
-    case 12: return launch_h2<64, 128, 32, 64, 2, 2, 128>(p, st);               // data-gradient chain of the training step takes the light
-    case 21: return launch_h2<256, 128, 64, 64, 3, 2, 34 + 128>(p, st);         // tile boundary and the 16-byte plane stores by shape, like
-    case 30: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 128>(p, st);    // the forward pass (the mask's loads are counted in `pend`)
-    case 31: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 128>(p, st);
-    case 32: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 512 + 128>(p, st);
-    case 33: return launch_h2<64, 128, 32, 64, 2, 2, 256 + 512 + 128>(p, st);
-    case 34: return launch_h2<256, 128, 64, 64, 3, 2, 34 + 512 + 128>(p, st);
-    case 40: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 1024 + 128>(p, st);
-    case 41: return launch_h2<64, 128, 32, 64, 2, 2, 256 + 512 + 1024 + 128>(p, st);
-    default: return FRCNN_E_ARG;
-  }
-  switch (cfg) {
-    case 9: return launch_h2<128, 128, 64, 64, 2, 2, 2>(p, st);  // 67 KB: 2 workgroups / CU, one barrier per slab, scales once per 128-k block
-    case 12: return launch_h2<64, 128, 32, 64, 2>(p, st);        // 64-row tiles, 4 waves of 32 x 64, 51 KB: 3 workgroups / CU (single-image launches)
-    case 21: return launch_h2<256, 128, 64, 64, 3, 2, 34>(p, st); // ping-pong: 256 x 128, 8 waves in two groups a segment apart, 3-slot ring
-    case 30: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256>(p, st);        // cfg 9 with the light tile boundary
-    case 31: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512>(p, st);  // ... and 16-byte plane stores
-    case 32: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 512>(p, st);        // cfg 9 with 16-byte plane stores only
-    case 33: return launch_h2<64, 128, 32, 64, 2, 2, 256 + 512>(p, st);       // cfg 12 with both
-    case 34: return launch_h2<256, 128, 64, 64, 3, 2, 34 + 512>(p, st);       // cfg 21 (ping-pong) with 16-byte plane stores
-    case 40: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 1024>(p, st);   // cfg 31 with the deferred epilogue (round 6)
-    case 41: return launch_h2<64, 128, 32, 64, 2, 2, 256 + 512 + 1024>(p, st);        // cfg 33 with the deferred epilogue
-#ifdef FRCNN_ABLATION
-    // measurement builds only (scratch/ablation_lib.py): the configurations the sweeps under profiles/r03_*, r04_* compare.  All of
-    // them multiply and fold in the same order as the three above (bit-identical results; measured, not shipped).
-    case 0: return launch_h2<128, 128, 64, 64, 2>(p, st);        // cfg 9 with the block scales in every stage
-    case 1: return launch_h2<128, 128, 64, 64, 3>(p, st);        // 100 KB: 1 workgroup / CU, 2 slabs in flight
-    case 2: return launch_h2<128, 128, 64, 64, 4>(p, st);        // 134 KB: 3 slabs in flight
-    case 3: return launch_h2<256, 128, 64, 64, 2>(p, st);        // 8 waves in lockstep, 100 KB
-    case 8: return launch_h2<128, 128, 64, 64, 2, 2, 1>(p, st);  // loads issued in two halves
-    case 13: return launch_h2<64, 128, 32, 64, 3>(p, st);        // 64-row tiles, 3-slot ring
-    case 15: return launch_h2<64, 128, 32, 64, 4>(p, st);        // ... 4-slot ring
-    case 14: return launch_h2<128, 128, 64, 64, 2, 2, 4>(p, st); // loads spread between the MFMAs (spills)
-    case 18: return launch_h2<128, 128, 64, 64, 2, 2, 10>(p, st); // round 2's (r >> 1) & 3 swizzle (two-way LDS bank conflicts)
-    case 24: return launch_h2<128, 128, 32, 64, 3, 2, 34>(p, st); // ping-pong on 128 x 128 tiles (8 waves of 32 x 64)
-    case 22: return launch_h2<256, 128, 64, 64, 3, 2, 34 + 64>(p, st);   // ping-pong with cache-resident X (wrong results by construction)
-    case 23: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 64>(p, st);    // cfg 9 with cache-resident X
-    case 20: return launch_h2<128, 128, 64, 64, 2, 2, 18>(p, st); // cfg 9's byte count as full-line loads (wrong results by construction)
-    // cache-policy experiments on the conv3 class (profiles/r06_h_*; all bit-identical, none shipped): `nt` on the once-touched streams
-    // (residual loads, result stores) 1 152 -> 1 472 us on block4 conv3 with MORE L2 misses; the 8 x 8 panel order 1 152 -> 1 138 us (-1.2 %,
-    // L2 misses -2 %: the residual / result streams dominate them) and +2 % on block3 conv3
-    case 42: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 1024 + 16384>(p, st);
-    case 43: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 1024 + 32768>(p, st);
-    case 44: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 1024 + 16384 + 32768>(p, st);
-    // the energy ledger (scratch/energy_ledger.py): cfg 31 with one ingredient of the slab loop taken out (wrong results by construction)
-    case 50: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 2048>(p, st);          // no MFMAs
-    case 51: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 4096>(p, st);          // no fragment reads (LDS -> registers)
-    case 52: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 8192>(p, st);          // no slab loads (L2 -> LDS) after the prologue
-    case 53: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 2048 + 4096>(p, st);   // loads + epilogue only
-    case 54: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 4096 + 8192>(p, st);   // MFMAs + epilogue only
-    case 55: return launch_h2<128, 128, 64, 64, 2, 2, 2 + 256 + 512 + 2048 + 4096 + 8192>(p, st);   // the epilogue (and the loop skeleton) only
-#endif
-    default: return FRCNN_E_ARG;
-  }
+  return p.mask ? h2_dispatch<H2_MASKED>(p, cfg, st) : h2_dispatch<0>(p, cfg, st);
 }
 
 // ---- frcnn_gemm_h2_mean: out[g * (M / rows) + r][n] = mean over the `rows` consecutive rows of group r of act(x[g] W^T + bias + res[g]) ------
@@ -1467,15 +1358,8 @@ extern "C" int frcnn_gemm_h2_mean(const void* x_planes_d, const float* x_inv_d, 
   if (K % H2_KB || N % 128 || M % rows || rows < 32 || 4ll * Mtot * K >= (1ll << 32) || 4ll * N * K >= (1ll << 32) || (long long)M * N >= (1ll << 29))
     return FRCNN_E_UNSUPPORTED;
   if (frcnn_gemm_h2_mean_workspace_bytes(G, M, N) > ws_bytes) return FRCNN_E_WS;
-  GemmH2Params p;
-  p.x = (const unsigned short*)x_planes_d; p.x_inv = x_inv_d; p.w = (const unsigned short*)w_planes_d; p.w_inv = w_inv_d;
-  p.bias = bias_d; p.res = res_d; p.resp = (const unsigned short*)res_planes_d; p.resp_inv = res_inv_d; p.y = nullptr; p.yp = nullptr; p.y_inv = nullptr;
-  p.M = M; p.N = N; p.K = K; p.batch = G; p.act = act; p.Mtot = Mtot;
-  p.nsteps = p.mtiles = p.ntiles = 0;
-#ifdef FRCNN_H2_TRACE
-  p.trace = g_h2_trace;
-#endif
-  p.mean_part = (float*)ws; p.mean_rows = rows; p.wshare = 1; p.mask = nullptr;
+  GemmH2Params p = h2_params(x_planes_d, x_inv_d, w_planes_d, w_inv_d, bias_d, res_d, res_planes_d, res_inv_d, nullptr, nullptr, nullptr, G, M, N, K, act);
+  p.mean_part = (float*)ws; p.mean_rows = rows; p.wshare = 1;
   hipStream_t st = (hipStream_t)stream;
   const int rc = run_h2(p, cfg, st);
   if (rc) return rc;

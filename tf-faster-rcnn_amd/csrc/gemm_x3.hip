@@ -65,8 +65,7 @@ __device__ __forceinline__ void x3_split8(const float4 a, const float4 b, bf16x8
   }
 }
 
-template <int BM, int BN, int WM, int WN, int ABL = 0, int TERMS = 6>   // ABL: compile-time ablations for measurements only (1: no operand split, 2: no slab
-                                                                     // loads after the first); TERMS = 9: also am*wl, al*wm, al*wl -> every product exact
+template <int BM, int BN, int WM, int WN, int TERMS = 6>   // TERMS = 9: also am*wl, al*wm, al*wl -> every product exact
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_waves_per_eu(2))) void k_gemm_x3(const GemmX3Params p) {
   constexpr int NW = (BM / WM) * (BN / WN);
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -164,12 +163,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         const char* q = sb + a_row + i * 32 * 128;
         const float4 f0 = *(const float4*)(q + (((4 * t + 2 * khalf) ^ a_sw) * 16));
         const float4 f1 = *(const float4*)(q + (((4 * t + 2 * khalf + 1) ^ a_sw) * 16));
-        if (ABL & 1) { ah[i] = __builtin_bit_cast(bf16x8, f0); am[i] = __builtin_bit_cast(bf16x8, f1); al[i] = ah[i]; }
-        else x3_split8(f0, f1, ah[i], am[i], al[i]);
+        x3_split8(f0, f1, ah[i], am[i], al[i]);
       }
       // the next slab's direct-to-LDS loads are spread over the two k groups
 #pragma unroll
-      for (int u = (t * G) / 2; u < ((t + 1) * G) / 2; ++u) if (!(ABL & 2)) issue_one(nbuf, u);
+      for (int u = (t * G) / 2; u < ((t + 1) * G) / 2; ++u) issue_one(nbuf, u);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -272,11 +270,11 @@ extern "C" int frcnn_gemm_x3_pack(const float* w_d, int G, int N, int K, void* p
   return FRCNN_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int ABL = 0, int TERMS = 6>
+template <int BM, int BN, int WM, int WN, int TERMS = 6>
 static int launch_x3(const GemmX3Params& q, hipStream_t st) {
   constexpr int NT = (BM / WM) * (BN / WN) * 64;
   constexpr size_t lds = 2 * (size_t)(BM * 128 + 3 * BN * 64);
-  auto kern = k_gemm_x3<BM, BN, WM, WN, ABL, TERMS>;
+  auto kern = k_gemm_x3<BM, BN, WM, WN, TERMS>;
   static KernelOnce once;
   int slots = 0;                            // resident workgroups on the CURRENT device
   HIP_TRY(kernel_once(once, (const void*)kern, NT, lds, &slots));
@@ -312,9 +310,9 @@ extern "C" int frcnn_gemm_x3(const float* x_d, const void* planes_d, const float
     cfg = (N % 128) ? 6 : ((long long)cdiv(M, 128) * (N / 128) * G >= 256) ? 0 : 1;
   if (terms == 9) {
     switch (cfg) {
-      case 0: return launch_x3<128, 128, 64, 64, 0, 9>(p, st);
-      case 1: return launch_x3<128, 128, 32, 64, 0, 9>(p, st);
-      case 6: return launch_x3<128, 64, 64, 32, 0, 9>(p, st);
+      case 0: return launch_x3<128, 128, 64, 64, 9>(p, st);
+      case 1: return launch_x3<128, 128, 32, 64, 9>(p, st);
+      case 6: return launch_x3<128, 64, 64, 32, 9>(p, st);
       default: return FRCNN_E_ARG;
     }
   }
@@ -326,14 +324,6 @@ extern "C" int frcnn_gemm_x3(const float* x_d, const void* planes_d, const float
     case 4: return launch_x3<256, 128, 64, 64>(p, st);        // 8 waves, 112 KB: 1 workgroup / CU, W slab shared by twice the rows
     case 5: return launch_x3<128, 256, 64, 64>(p, st);        // 8 waves, 128 KB
     case 6: return launch_x3<128, 64, 64, 32>(p, st);         // N % 64 == 0: 4 waves of 64x32, 56 KB
-#ifdef FRCNN_ABLATION                                          // measurement builds only (wrong results by construction): not in the shipped library
-    case 10: return launch_x3<128, 128, 64, 64, 1>(p, st);
-    case 11: return launch_x3<128, 128, 64, 64, 2>(p, st);
-    case 12: return launch_x3<128, 128, 64, 64, 3>(p, st);
-    case 13: return launch_x3<128, 128, 32, 64, 1>(p, st);
-    case 14: return launch_x3<128, 128, 32, 64, 2>(p, st);
-    case 15: return launch_x3<128, 128, 32, 64, 3>(p, st);
-#endif
     default: return FRCNN_E_ARG;
   }
 }

@@ -245,7 +245,7 @@ int frcnn_conv2d_nhwc_ws(const float* x_d, int N, int H, int W, int Cin, const f
 
 /* Tuning overrides for A/B measurements and for tests that must reach every tile configuration: THREAD-LOCAL (they affect only the
  * launches the calling thread makes afterwards, so the thread-safety contract above holds); no product path sets keys 0-7.  key 0 = force a
- * conv tile configuration id (-1 = automatic); key 1 = ablation bits; key 5 = phase stagger of co-resident workgroups; key 6 = 0 keeps
+ * conv tile configuration id (-1 = automatic; an id that does not exist makes the convolution return FRCNN_E_ARG); key 5 = phase stagger of co-resident workgroups; key 6 = 0 keeps
  * the short-K GEMMs off k_gemm_stream; key 7 = the workgroup count a split-K launch aims at (0 = the default 640; 160 ... 640 move the
  * ResNet-152 training step by +-1 %); key 9 = the workgroup count below which the F(4x4,3x3) Winograd transforms run in their
  * row-per-thread form (0 = the default 256; both forms give the same bits).  frcnn_gemm_x3 / frcnn_gemm_h2 take their configuration per call instead.

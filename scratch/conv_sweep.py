@@ -1,5 +1,9 @@
-"""A/B harness: configurations interleaved in rounds inside one process, median over rounds."""
-import sys, os, itertools
+"""A/B harness: tile configurations (ids of tuning key 0: k_conv_igemm and, from 100 on, k_gemm_stream) interleaved in rounds inside one
+process, median over rounds.
+
+    python scratch/conv_sweep.py CFG[,CFG...] [SHAPE[,SHAPE...] [ROUNDS]]
+"""
+import sys, os
 sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tf-faster-rcnn_amd")]
 import numpy as np, torch
 from frcnn_hip import ops, lib
@@ -16,29 +20,33 @@ shapes = {  # name: (N,H,W,Cin,Cout,k,pad)
  "b4c1": (300,7,7,2048,512,1,0), "b4c2": (300,7,7,512,512,3,1), "b4c3": (300,7,7,512,2048,1,0),
 }
 cfgs = [int(c) for c in sys.argv[1].split(",")]
-dbgs = [int(c) for c in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0]
-only = sys.argv[3].split(",") if len(sys.argv) > 3 else list(shapes)
-rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 5
-print("%-6s %4s %3s %9s %9s %8s" % ("shape", "cfg", "dbg", "med_us", "min_us", "TFLOP/s"))
+only = sys.argv[2].split(",") if len(sys.argv) > 2 else list(shapes)
+rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+
+
+def tune(key, value):
+    rc = L.frcnn_set_tuning(key, value)
+    if rc:
+        raise SystemExit("frcnn_set_tuning(%d, %d) returned %d" % (key, value, rc))
+
+
+print("%-6s %4s %9s %9s %8s" % ("shape", "cfg", "med_us", "min_us", "TFLOP/s"))
 for name in only:
     N,H,W,Cin,Cout,k,pad = shapes[name]
     x = torch.randn(N,H,W,Cin, device=dev); w = torch.randn(Cout,k,k,Cin, device=dev) * 0.05; b = torch.randn(Cout, device=dev)
     res = torch.randn(N,H,W,Cout, device=dev) if name.endswith("c3") else None
     out = torch.empty(N,H,W,Cout, device=dev)
     flops = 2.0*N*H*W*Cout*k*k*Cin
-    combos = list(itertools.product(cfgs, dbgs))
-    times = {c: [] for c in combos}
+    times = {c: [] for c in cfgs}
     for r in range(rounds + 1):
-        for cfg, dbg in combos:
-            if cfg >= 100: L.frcnn_set_tuning(2, 1); L.frcnn_set_tuning(3, cfg - 100)
-            else: L.frcnn_set_tuning(2, 0); L.frcnn_set_tuning(0, cfg)
-            L.frcnn_set_tuning(1, dbg)
+        for cfg in cfgs:
+            tune(0, cfg)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            for _ in range(8): ops.conv2d(x, w, b, k, k, 1, (pad,)*4, 1, res, 1, out=out)
+            for _ in range(8): ops.conv2d(x, w, b, k, k, 1, (pad,)*4, 1, res, 1, out=out)      # raises when the launch reports an error
             e1.record(); torch.cuda.synchronize()
-            if r: times[(cfg, dbg)].append(e0.elapsed_time(e1) * 1000 / 8)
-    for (cfg, dbg), ts in times.items():
+            if r: times[cfg].append(e0.elapsed_time(e1) * 1000 / 8)
+    for cfg, ts in times.items():
         med = float(np.median(ts))
-        print("%-6s %4d %3d %9.1f %9.1f %8.1f" % (name, cfg, dbg, med, min(ts), flops / med / 1e6))
-L.frcnn_set_tuning(0, -1); L.frcnn_set_tuning(1, 0); L.frcnn_set_tuning(2, 0); L.frcnn_set_tuning(3, -1)
+        print("%-6s %4d %9.1f %9.1f %8.1f" % (name, cfg, med, min(ts), flops / med / 1e6))
+tune(0, -1)

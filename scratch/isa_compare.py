@@ -4,7 +4,8 @@
     python scratch/isa_compare.py before.s after.s [--rename REGEX REPL] [--only REGEX] [--label TEXT]
 
 For every kernel (a symbol with an .amdhsa_kernel descriptor) the lines between its label and its .Lfunc_end, and its .amdhsa_* block,
-must be textually identical; .file / .ident / .loc directives are ignored.  --rename rewrites symbol names in both files first (a removed
+must be textually identical; .file / .ident / .loc directives are ignored, and so is the function ordinal in basic-block labels
+(.LBB<function>_<block>: the function's position in the translation unit, which moves when other kernels are removed).  --rename rewrites symbol names in both files first (a removed
 template parameter), --only restricts the kernels of `before` that are expected in `after`.  Prints one line per kernel; exit status 1
 on any difference.
 """
@@ -13,6 +14,8 @@ import re
 import sys
 
 SKIP = re.compile(r"^\s*\.(file|ident|loc|cfi_\w+)\b")
+BLOCK = re.compile(r"BB\d+_(\d+)")
+PAD = re.compile(r"\s+;")            # the comment column after a label depends on the label's length
 
 
 def kernels(path, rename):
@@ -30,7 +33,7 @@ def kernels(path, rename):
         desc = [l.strip() for l in lines[i : j + 1]]
         b = next(k for k, l in enumerate(lines) if l.startswith(name + ":"))
         e = next(k for k in range(b, len(lines)) if lines[k].startswith(".Lfunc_end"))
-        body = [l for l in lines[b:e] if not SKIP.match(l)]
+        body = [PAD.sub(" ;", BLOCK.sub(r"BB_\1", l)) for l in lines[b:e] if not SKIP.match(l)]
         ninstr = sum(1 for l in body if re.match(r"\t[a-z]\w+", l) and not l.lstrip().startswith("."))
         info = {k: next((re.search(r"(\d+)", l.split(k)[1]).group(1) for l in lines[e : e + 40] if k in l), "?")
                 for k in (" NumVgprs:", " NumAgprs:", " TotalNumSgprs:", " AccumOffset:", " ScratchSize:", " LDSByteSize:")}

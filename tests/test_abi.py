@@ -79,3 +79,19 @@ def test_error_codes_without_gpu():
     assert L.frcnn_proposal_workspace_bytes(38, 63, 9, 6000) > 0
     assert L.frcnn_detect_post_workspace_bytes(300, 21) > 0
     assert L.frcnn_conv2d_nhwc(None, 1, 1, 1, 32, None, None, None, 0, 0, 1, None, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, None) == -1
+
+
+def test_set_tuning_keys():
+    """frcnn_set_tuning (thread-local state, no GPU needed): keys 1 and 2 do not exist; keys 0, 5, 6, 7, 8, 9 do."""
+    import frcnn_hip
+    L = frcnn_hip.lib()
+    E_ARG, OK = -1, 0
+    defaults = {0: -1, 5: 0, 6: 1, 7: 0, 8: 0, 9: 0}
+    try:
+        assert L.frcnn_set_tuning(1, 0) == E_ARG
+        assert L.frcnn_set_tuning(2, 0) == E_ARG
+        for key in defaults:
+            assert L.frcnn_set_tuning(key, 1) == OK, key
+    finally:
+        for key, value in defaults.items():
+            assert L.frcnn_set_tuning(key, value) == OK, key

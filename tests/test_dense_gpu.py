@@ -376,7 +376,7 @@ def test_pointwise_conv_streaming_gemm(dev, case):
         torch.cuda.synchronize()
         got = out.cpu().numpy().copy()
         assert bool((guard[M:] == 7.25).all()), "store past the last row"
-        L.frcnn_set_tuning(0, 15)                                                    # k_conv_igemm <64,64,32,32> (k split over two accumulators)
+        L.frcnn_set_tuning(0, 15)                                                    # IGEMM_64x64_ILV: k_conv_igemm <64,64,32,32> (k split over two accumulators)
         ref15 = ops.conv2d(xd, wp, bd, 1, 1, 1, (0, 0, 0, 0), act, rd, 1)
         torch.cuda.synchronize()
     finally:
@@ -416,6 +416,25 @@ def test_streaming_gemm_configurations_bit_identical_to_igemm(dev, cfg, base):
     assert np.array_equal(res[cfg][1], res[base][1])
     want = torch.einsum("gmk,gnk->gmn", xg.double().cpu(), wg.double().cpu()).numpy()
     assert float(np.abs(res[cfg][1] - want).max()) <= 2e-5 * max(1.0, float(np.abs(want).max()))
+
+
+def test_removed_tile_configuration_is_refused_before_any_launch(dev):
+    """a k_conv_igemm (3) / k_gemm_stream (113) configuration id that no longer exists: the argument error, and nothing written"""
+    import frcnn_hip
+    from frcnn_hip import ops, lib
+    x = torch.ones(1, 1, 64, 32, dtype=torch.float32, device=dev)
+    wp = torch.ones(32, 1, 1, 32, dtype=torch.float32, device=dev)
+    out = torch.full((1, 1, 64, 32), float("nan"), dtype=torch.float32, device=dev)
+    L = lib()
+    try:
+        for cfg in (3, 113):
+            assert L.frcnn_set_tuning(0, cfg) == 0
+            with pytest.raises(frcnn_hip.FrcnnHipError, match="bad argument"):
+                ops.conv2d(x, wp, None, 1, 1, out=out)
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(out).all()), cfg
+    finally:
+        L.frcnn_set_tuning(0, -1)
 
 
 X3_CASES = [

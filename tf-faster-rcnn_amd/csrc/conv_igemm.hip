@@ -27,10 +27,9 @@
 // lib/nets/resnet_v1.py:80-125 (7x7/2 stem via fold_w, bottleneck 1x1 / 3x3 / conv2d_same
 // stride 2, projection and subsample shortcuts), vgg16.py:26-60.
 #include "common.h"
+#include "mfma_f32.h"
 #include <mutex>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ float4 g_zero_page[4];     // 64 zero bytes (static device memory, zero-initialised)
 
@@ -43,36 +42,41 @@ struct ConvParams {
   int mtiles, ntiles;
   int batch;                       // grid.y (1 for convolutions)
   long long gx, gw, gy;            // batched GEMM use (grid.y = batch index): element strides of x / w / y per batch
-  int dbg;                         // unused by the kernels (kept for the tuning ABI); run-time switches in the hot loop cost MFMA issue slots
+  int reserved;                    // always 0: the slot of a removed tuning value, kept so that the kernel-argument offsets after it do not move
   int splits, kchunk;              // split-K: grid.z = splits, each covers kchunk slabs and writes raw partial sums to y + z*gz
   long long gz;
   int stagger, stagger_slots;      // > 0: workgroup in residency slot s of its CU (first dispatch round) starts s * stagger shader cycles late
 };
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+// Element offset of the residual of output (m, n) at res_stride > 1: pixel (oh, ow) * res_stride of an [img][RH][RW][Cout] tensor
+// (subsample shortcuts); ohow = OH * OW.  At res_stride 1 the residual has the output's own offset.
+__device__ __forceinline__ size_t res_offset_strided(int m, int n, int Cout, int res_stride, int ohow, int OW, int RH, int RW) {
+  const int img = m / ohow, rem = m % ohow, oh = rem / OW, ow = rem % OW;
+  return ((size_t)(img * RH + oh * res_stride) * RW + ow * res_stride) * Cout + n;
 }
 
-// One direct-to-LDS load: 64 lanes x 16 B from per-lane global addresses to LDS [lds_base, +1 KiB),
-// lane-linear.  Issued from inline asm on purpose: hipcc tracks builtin LDS-DMA conservatively and
-// puts `s_waitcnt vmcnt(0)` in front of the first ds_read of every k-step (it cannot prove the ring
-// slots disjoint), which would drain the NS-deep pipeline; asm loads are invisible to its scoreboard,
-// so the counted waits below are the only ones.  M0 (LDS base) is saved/restored inside the statement.
-__device__ __forceinline__ void glds16(const float* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
+// The fragment reads and the MFMA order of one k-group (8 of a slab's 32 k), stated once for k_conv_igemm and k_gemm_stream.
+template <int TM, int TN>
+__device__ __forceinline__ void frag_read(float4 (&a)[TM], const float* sb, const int& a_row0, const int& koff, float4 (&b)[TN], const int& b_row0) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i) a[i] = *(const float4*)(sb + a_row0 + i * 1024 + koff);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) b[j] = *(const float4*)(sb + b_row0 + j * 1024 + koff);
+}
+template <int TM, int TN>
+__device__ __forceinline__ void frag_mfma(const float4 (&a)[TM], const float4 (&b)[TN], f32x16 (&acc2)[TM][TN], f32x16 (&acc)[TM][TN]) {
+  constexpr bool KSPLIT = (TM * TN == 1);
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const float av = e == 0 ? a[i].x : e == 1 ? a[i].y : e == 2 ? a[i].z : a[i].w;
+        const float bv = e == 0 ? b[j].x : e == 1 ? b[j].y : e == 2 ? b[j].z : b[j].w;
+        if (KSPLIT && (e & 1)) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc2[i][j], 0, 0, 0);
+        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
+      }
 }
 
 template <int BM, int BN, int WM, int WN, int NS, bool FOLDW, bool ILV = false, bool RF = false>
@@ -210,7 +214,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_conv_igemm(const
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acc2[i][j][r] = 0.f; }
 
-  // fragment read offsets: row (lane&31) of the wave's 32-row groups, k chunk 2s + (lane>>5), swizzled
+  // fragment read offsets: row (lane&31) of the wave's 32-row groups, k chunk 2s + (lane>>5), swizzled.  TWIN: these offsets and the
+  // slab orderings of `slab` below are repeated in k_gemm_stream (koff / slab_body); as shared functions they move instructions.
   const int frow = lane & 31, khalf = lane >> 5;
   int koff[4];
 #pragma unroll
@@ -236,27 +241,10 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_conv_igemm(const
     const int nbuf = (step + P) % NS;
     const float* sb = smem + (step % NS) * SLAB;
     float4 a[4][TM], b[4][TN];
-    auto read_frag = [&](int q) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[q][i] = *(const float4*)(sb + a_row0 + i * 1024 + koff[q]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[q][j] = *(const float4*)(sb + b_row0 + j * 1024 + koff[q]);
-    };
+    auto read_frag = [&](int q) { frag_read(a[q], sb, a_row0, koff[q], b[q], b_row0); };
     // MFMA order: consecutive instructions always target DIFFERENT accumulators; single-tile waves split k over two
     // accumulators (KSPLIT)
-    auto mfma_group = [&](int q) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float av = e == 0 ? a[q][i].x : e == 1 ? a[q][i].y : e == 2 ? a[q][i].z : a[q][i].w;
-            const float bv = e == 0 ? b[q][j].x : e == 1 ? b[q][j].y : e == 2 ? b[q][j].z : b[q][j].w;
-            if (KSPLIT && (e & 1)) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc2[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-          }
-    };
+    auto mfma_group = [&](int q) { frag_mfma(a[q], b[q], acc2, acc); };
     if (ILV) {
       // the wave's G slab loads are spread between the four k-groups so that their issue slots hide behind MFMAs; group q+1's
       // fragment reads are written BEFORE group q's loads (the asm loads carry a memory clobber, reads cannot cross them)
@@ -331,10 +319,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_conv_igemm(const
       if (p.res) {
         size_t ro;
         if (p.res_stride == 1) ro = (size_t)m * p.Cout + n;
-        else {
-          const int img = m / ohow, rem = m % ohow, oh = rem / p.OW, ow = rem % p.OW;
-          ro = ((size_t)(img * p.RH + oh * p.res_stride) * p.RW + ow * p.res_stride) * p.Cout + n;
-        }
+        else ro = res_offset_strided(m, n, p.Cout, p.res_stride, ohow, p.OW, p.RH, p.RW);
         const float4 rv = *(const float4*)(p.res + ro);
         v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
       }
@@ -356,10 +341,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_conv_igemm(const
       if (p.res) {
         size_t ro;
         if (p.res_stride == 1) ro = (size_t)m * p.Cout + n;
-        else {
-          const int img = m / ohow, rem = m % ohow, oh = rem / p.OW, ow = rem % p.OW;
-          ro = ((size_t)(img * p.RH + oh * p.res_stride) * p.RW + ow * p.res_stride) * p.Cout + n;
-        }
+        else ro = res_offset_strided(m, n, p.Cout, p.res_stride, ohow, p.OW, p.RH, p.RW);
         v += p.res[ro];
       }
       if (p.act == FRCNN_ACT_RELU) v = act_relu(v);
@@ -474,7 +456,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_gemm_stream(cons
         for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acc2[i][j][r] = 0.f; }
   };
   zero_acc();
-  const int frow = lane & 31, khalf = lane >> 5;
+  const int frow = lane & 31, khalf = lane >> 5;                   // TWIN of k_conv_igemm's fragment read offsets
   int koff[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) koff[s] = ((2 * s + khalf) ^ ((frow >> 1) & 7)) * 4;
@@ -510,30 +492,14 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void k_gemm_stream(cons
 
   // The multiply part of one slab: fragment reads of slab `cur`, the direct-to-LDS loads of the stream's next slab, 64 * TM * TN
   // MFMAs.  ONE code instance for every slab of every tile (no branch inside: a branch would split the block and the compiler
-  // would then serialise fragment reads and MFMAs).
+  // would then serialise fragment reads and MFMAs).  TWIN: the ILV / RF orderings below repeat k_conv_igemm's `slab` with every slab
+  // issued (its MORE case); the reads and the MFMA order themselves are frag_read / frag_mfma, shared.
   auto slab_body = [&](int cur) {
     const int nbuf = cur ^ 1;
     const float* sb = smem + cur * SLAB;
     float4 a[4][TM], b[4][TN];
-    auto read_frag = [&](int q) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[q][i] = *(const float4*)(sb + a_row0 + i * 1024 + koff[q]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[q][j] = *(const float4*)(sb + b_row0 + j * 1024 + koff[q]);
-    };
-    auto mfma_group = [&](int q) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float av = e == 0 ? a[q][i].x : e == 1 ? a[q][i].y : e == 2 ? a[q][i].z : a[q][i].w;
-            const float bv = e == 0 ? b[q][j].x : e == 1 ? b[q][j].y : e == 2 ? b[q][j].z : b[q][j].w;
-            if (KSPLIT && (e & 1)) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc2[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-          }
-    };
+    auto read_frag = [&](int q) { frag_read(a[q], sb, a_row0, koff[q], b[q], b_row0); };
+    auto mfma_group = [&](int q) { frag_mfma(a[q], b[q], acc2, acc); };
     if (ILV) {
       read_frag(0);
 #pragma unroll
@@ -643,32 +609,50 @@ static int launch_stream(const ConvParams& c, hipStream_t st) {
   return FRCNN_OK;
 }
 
-// streaming configurations (ids 100+ of tuning key 0)
-static int launch_stream_cfg(int id, const ConvParams& p, hipStream_t st) {
+// Tile configurations by id (tuning key 0; tests, bench.py --tune 0=N and scratch/stream_sweep.py pass the numbers).  The ids are the
+// survivors of the closed sweeps (profiles/README.md), which is why they are not contiguous.
+enum : int {
+  IGEMM_64x32_NS4 = 4,              // k_conv_igemm: 4-deep ring
+  IGEMM_64x64_ILV = 15,             // 32 KB LDS: up to 5 workgroups / CU, loads interleaved with MFMAs
+  IGEMM_128_RF = 20,                // 128x128, 4 waves x 64x64, reads first
+  IGEMM_128_8W_RF = 21,             // 128x128, 8 waves x 32x64 (2 accumulators each), reads first
+  // k_gemm_stream from here on; *_RESPF: residual rows requested before the last slab's MFMAs
+  STREAM_64x64 = 100, STREAM_64x64_RESPF = 101,
+  STREAM_128_RF = 102,
+  STREAM_128_8W_RF = 104, STREAM_128_8W_RF_RESPF = 105,
+  STREAM_128x64 = 106, STREAM_128x64_RESPF = 107,                 // 8 single-tile waves, 48 KB
+  STREAM_64x128 = 108, STREAM_64x128_RESPF = 109,
+  STREAM_128x64_4W_RESPF = 110, STREAM_64x128_4W_RESPF = 111,     // 4 waves x 2 accumulators
+  STREAM_32x64 = 112,                                             // 2 single-tile waves, 24 KB
+  STREAM_32x128 = 114,                                            // 4 single-tile waves, 40 KB
+};
+
+static int launch_cfg(int id, const ConvParams& p, hipStream_t st) {
   switch (id) {
-    case 100: return launch_stream<64, 64, 32, 32, true, false, false>(p, st);      // cfg 15
-    case 101: return launch_stream<64, 64, 32, 32, true, false, true>(p, st);
-    case 102: return launch_stream<128, 128, 64, 64, false, true, false>(p, st);    // cfg 20
-    case 103: return launch_stream<128, 128, 64, 64, false, true, true>(p, st);
-    case 104: return launch_stream<128, 128, 32, 64, false, true, false>(p, st);    // cfg 21
-    case 105: return launch_stream<128, 128, 32, 64, false, true, true>(p, st);
-    case 106: return launch_stream<128, 64, 32, 32, true, false, false>(p, st);     // 8 single-tile waves, 48 KB
-    case 107: return launch_stream<128, 64, 32, 32, true, false, true>(p, st);
-    case 108: return launch_stream<64, 128, 32, 32, true, false, false>(p, st);
-    case 109: return launch_stream<64, 128, 32, 32, true, false, true>(p, st);
-    case 110: return launch_stream<128, 64, 64, 32, false, true, true>(p, st);      // 4 waves x 2 accumulators
-    case 111: return launch_stream<64, 128, 32, 64, false, true, true>(p, st);
-    case 112: return launch_stream<32, 64, 32, 32, true, false, false>(p, st);       // 2 single-tile waves, 24 KB
-    case 113: return launch_stream<64, 32, 32, 32, true, false, false>(p, st);
-    case 114: return launch_stream<32, 128, 32, 32, true, false, false>(p, st);      // 4 single-tile waves, 40 KB
-    case 115: return launch_stream<32, 64, 32, 32, false, true, false>(p, st);
-    default: return FRCNN_E_ARG;
+    case IGEMM_64x32_NS4: return launch_conv<64, 32, 32, 32, 4, false>(p, st);
+    case IGEMM_64x64_ILV: return launch_conv<64, 64, 32, 32, 2, false, true>(p, st);
+    case IGEMM_128_RF: return launch_conv<128, 128, 64, 64, 2, false, false, true>(p, st);
+    case IGEMM_128_8W_RF: return launch_conv<128, 128, 32, 64, 2, false, false, true>(p, st);
+    case STREAM_64x64: return launch_stream<64, 64, 32, 32, true, false, false>(p, st);
+    case STREAM_64x64_RESPF: return launch_stream<64, 64, 32, 32, true, false, true>(p, st);
+    case STREAM_128_RF: return launch_stream<128, 128, 64, 64, false, true, false>(p, st);
+    case STREAM_128_8W_RF: return launch_stream<128, 128, 32, 64, false, true, false>(p, st);
+    case STREAM_128_8W_RF_RESPF: return launch_stream<128, 128, 32, 64, false, true, true>(p, st);
+    case STREAM_128x64: return launch_stream<128, 64, 32, 32, true, false, false>(p, st);
+    case STREAM_128x64_RESPF: return launch_stream<128, 64, 32, 32, true, false, true>(p, st);
+    case STREAM_64x128: return launch_stream<64, 128, 32, 32, true, false, false>(p, st);
+    case STREAM_64x128_RESPF: return launch_stream<64, 128, 32, 32, true, false, true>(p, st);
+    case STREAM_128x64_4W_RESPF: return launch_stream<128, 64, 64, 32, false, true, true>(p, st);
+    case STREAM_64x128_4W_RESPF: return launch_stream<64, 128, 32, 64, false, true, true>(p, st);
+    case STREAM_32x64: return launch_stream<32, 64, 32, 32, true, false, false>(p, st);
+    case STREAM_32x128: return launch_stream<32, 128, 32, 32, true, false, false>(p, st);
+    default: return FRCNN_E_ARG;          // a removed or unknown id: refused before any launch
   }
 }
 
 // tuning knob (experiments / A-B runs): key 0 = force a tile configuration id for every non-stem conv
 // (-1 = automatic choice).
-static thread_local int g_force_cfg = -1, g_dbg = 0, g_stagger = 0, g_stream = 1, g_split_target = 640;      // per calling thread: no state shared between threads
+static thread_local int g_force_cfg = -1, g_stagger = 0, g_stream = 1, g_split_target = 640;      // per calling thread: no state shared between threads
 // key 8: the launches that follow carry this many independent images (a TEST-mode batch).  Split-K changes the order in which a sum is
 // formed, so its plan must not depend on how many images share a launch: it is made for the launch as it would look in a batch of
 // PLAN_IMAGES images (per-image rows x 4: the plan of the 4-image batches the throughput configuration runs), whatever the actual
@@ -679,42 +663,11 @@ extern thread_local int g_wino_rows_below;              // csrc/winograd.hip: wo
 extern "C" int frcnn_set_tuning(int key, int value) {
   if (key == 9) { g_wino_rows_below = value > 0 ? value : 256; return FRCNN_OK; }
   if (key == 0) { g_force_cfg = value; return FRCNN_OK; }
-  if (key == 1) { g_dbg = value; return FRCNN_OK; }
   if (key == 5) { g_stagger = value; return FRCNN_OK; }        // 0 off; n > 0: second-slot workgroups start n/8 of a tile late
   if (key == 6) { g_stream = value; return FRCNN_OK; }         // 0: never dispatch to k_gemm_stream (A/B runs)
   if (key == 7) { g_split_target = value > 0 ? value : 640; return FRCNN_OK; }   // workgroups a split-K launch aims at (plan_splits)
   if (key == 8) { g_plan_images = value > 0 ? value : 0; return FRCNN_OK; }      // images sharing the next launches (batch-invariant split plan)
   return FRCNN_E_ARG;
-}
-
-static int launch_cfg(int id, const ConvParams& p, hipStream_t st) {
-  switch (id) {
-    case 0: return launch_conv<128, 128, 64, 64, 2, false>(p, st);   // 64 KB LDS: 2 workgroups / CU
-    case 1: return launch_conv<128, 128, 64, 64, 3, false>(p, st);   // 96 KB: 1 workgroup / CU, 2 slabs ahead
-    case 2: return launch_conv<64, 64, 32, 32, 4, false>(p, st);
-    case 3: return launch_conv<32, 64, 32, 32, 4, false>(p, st);
-    case 4: return launch_conv<64, 32, 32, 32, 4, false>(p, st);
-    case 5: return launch_conv<128, 64, 64, 32, 3, false>(p, st);
-    case 6: return launch_conv<64, 128, 32, 64, 3, false>(p, st);
-    case 7: return launch_conv<64, 64, 32, 32, 2, false>(p, st);
-    case 8: return launch_conv<32, 64, 32, 32, 2, false>(p, st);
-    case 9: return launch_conv<32, 32, 32, 32, 4, false>(p, st);
-    case 10: return launch_conv<128, 128, 32, 64, 2, false>(p, st);  // 8 waves, 2 accumulators each
-    case 11: return launch_conv<128, 128, 32, 64, 3, false, true>(p, st);   // 96 KB ring, loads interleaved with MFMAs
-    case 12: return launch_conv<128, 128, 32, 64, 2, false, true>(p, st);
-    case 13: return launch_conv<128, 256, 64, 64, 2, false>(p, st);         // 8 waves x 64x64, 96 KB, 1 workgroup / CU
-    case 14: return launch_conv<128, 256, 64, 64, 2, false, true>(p, st);
-    case 15: return launch_conv<64, 64, 32, 32, 2, false, true>(p, st);
-    case 16: return launch_conv<128, 128, 64, 64, 2, false, true>(p, st);
-    case 17: return launch_conv<128, 64, 64, 32, 2, false>(p, st);          // 48 KB: 3 workgroups / CU
-    case 18: return launch_conv<64, 128, 32, 64, 2, false>(p, st);
-    case 19: return launch_conv<128, 64, 32, 32, 2, false>(p, st);          // 8 single-tile waves
-    case 20: return launch_conv<128, 128, 64, 64, 2, false, false, true>(p, st);   // reads-first variants of 0 / 10 / 7 / 4
-    case 21: return launch_conv<128, 128, 32, 64, 2, false, false, true>(p, st);
-    case 22: return launch_conv<64, 64, 32, 32, 2, false, false, true>(p, st);
-    case 23: return launch_conv<64, 32, 32, 32, 4, false, false, true>(p, st);
-    default: return FRCNN_E_ARG;
-  }
 }
 
 // ---- split-K for under-filled launches ------------------------------------------------------------------------------
@@ -727,11 +680,32 @@ static long long plan_rows(long long M) {
   return (g_plan_images > 0 && M % g_plan_images == 0) ? M / g_plan_images * PLAN_IMAGES : M;
 }
 
+// 128x128 tiles of `groups` problems of rows x Cout
+static long long tiles_128(long long rows, int Cout, int groups) { return (rows + 127) / 128 * cdiv(Cout, 128) * groups; }
+
+// THE tile rule, from the measured sweep (profiles/r01_conv_tile_sweep.txt).  f32 MFMA needs few bytes per FLOP, so the limiter is never
+// LDS or HBM but (a) how many of the 1024 SIMDs get a wave and (b) the per-slab barrier/ds_read overhead: 128x128 tiles (a tile keeps
+// each SIMD's matrix pipe busy for nsteps * 64 MFMAs * 64 cycles; two workgroups share a CU; reads-first, and 8 waves help the residual
+// epilogue of the widest outputs) for launches that fill the machine with them, 64-row tiles with a shallow ring (32 KB LDS -> up to 5
+// workgroups per CU) for the 38x63 / 75x125 / 150x250 feature maps.  The configurations do not all add in the same order (8-wave tiles
+// keep two accumulators per sub-tile), so `rows` are the PLANNED rows (plan_rows, key 8), not the rows of one particular launch.
+static int tile_cfg_64(int Cout) { return Cout > 32 ? IGEMM_64x64_ILV : IGEMM_64x32_NS4; }
+static int tile_cfg(long long rows, int Cout, int nsteps, int groups) {
+  if (Cout >= 96 && tiles_128(rows, Cout, groups) >= 384 && nsteps >= 8) return Cout >= 1024 ? IGEMM_128_8W_RF : IGEMM_128_RF;
+  return tile_cfg_64(Cout);
+}
+
+// Short-K products (bottleneck conv3: K = Cin <= 256 into a 4x wider output + residual; the batched Winograd products): a tile is only
+// <= 8 slabs (<= 128 MFMAs per wave), so per-tile launch / prologue / LDS-staged epilogue cost as much as the multiply -> resident
+// streaming workers with register epilogues (profiles/r02_h_stream_sweep.txt: 64.5 -> 51 us on 9576 x 1024 x 256).
+static bool short_k_stream(long long rows, int Cout, int nsteps, int groups) {
+  return g_stream && nsteps <= 8 && Cout % 128 == 0 && (rows + 63) / 64 * (Cout / 128) * groups >= 512;
+}
+
 static int plan_splits(int M, int Cout, int nsteps) {
   if (g_force_cfg >= 0) return 1;
   M = (int)min(plan_rows(M), (long long)0x7fffffff);
-  const long long big = (long long)cdiv(M, 128) * cdiv(Cout, 128);
-  if (Cout >= 96 && big >= 384 && nsteps >= 8) return 1;
+  if (tile_cfg(M, Cout, nsteps, 1) != tile_cfg_64(Cout)) return 1;                    // only launches of 64-row tiles are cut
   const long long tiles = (long long)cdiv(M, 64) * cdiv(Cout, Cout > 32 ? 64 : 32);
   if (tiles >= 384 || nsteps < 16) return 1;
   int S = (int)min((long long)8, (g_split_target + tiles - 1) / tiles);
@@ -762,10 +736,7 @@ __global__ void k_splitk_finish(const float* __restrict__ part, int S, int M, in
     if (res) {
       size_t ro;
       if (res_stride == 1) ro = (size_t)i;
-      else {
-        const int img = m / ohow, rem = m % ohow, oh = rem / OW, ow = rem % OW;
-        ro = ((size_t)(img * RH + oh * res_stride) * RW + ow * res_stride) * Cout + n;
-      }
+      else ro = res_offset_strided(m, n, Cout, res_stride, ohow, OW, RH, RW);
       v += res[ro];
     }
     if (act == FRCNN_ACT_RELU) v = act_relu(v);
@@ -775,10 +746,75 @@ __global__ void k_splitk_finish(const float* __restrict__ part, int S, int M, in
   }
 }
 
+// Every field at its neutral value: a 1x1 stride-1 unpadded filter, nothing fused, one problem, no split-K, no stagger.  The callers set
+// what differs.
+static ConvParams conv_params() {
+  ConvParams p = {};
+  p.KH = p.KW = p.stride = p.res_stride = p.batch = p.splits = 1;
+  p.act = FRCNN_ACT_NONE;
+  return p;
+}
+
 static int conv2d_impl(const float* x_d, int N, int H, int W, int Cin, const float* w_d, const float* bias_d,
                        const float* residual_d, int RH, int RW, int res_stride, float* y_d, int OH, int OW, int Cout, int KH, int KW,
                        int stride, int pad_top, int pad_left, int act, int fold_w, void* ws, size_t ws_bytes, const float* mask_d,
-                       void* stream);
+                       void* stream) {
+  if (!x_d || !w_d || !y_d) return FRCNN_E_ARG;
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || OH <= 0 || OW <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0)
+    return FRCNN_E_ARG;
+  if (act < 0 || act > 2) return FRCNN_E_ARG;
+  if (residual_d && (res_stride < 1 || RH < (OH - 1) * res_stride + 1 || RW < (OW - 1) * res_stride + 1)) return FRCNN_E_ARG;
+  if (fold_w) {
+    if (Cin != 4 || KW > 8) return FRCNN_E_UNSUPPORTED;
+  } else if (Cin % 32) {
+    return FRCNN_E_UNSUPPORTED;
+  }
+  if ((long long)N * H * W * Cin >= (1ll << 31) || (long long)N * OH * OW >= (1ll << 31) / 4) return FRCNN_E_UNSUPPORTED;
+  ConvParams p = conv_params();
+  p.x = x_d; p.w = w_d; p.bias = bias_d; p.res = residual_d; p.y = y_d; p.mask = mask_d;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout; p.KH = KH; p.KW = fold_w ? 1 : KW;
+  p.stride = stride; p.pad_top = pad_top; p.pad_left = pad_left; p.act = act;
+  p.RH = RH; p.RW = RW; p.res_stride = residual_d ? res_stride : 1;
+  p.M = N * OH * OW;
+  p.Ktot = fold_w ? KH * 32 : KH * KW * Cin;
+  p.nsteps = p.kchunk = fold_w ? KH : KH * KW * (Cin / 32);
+  hipStream_t st = (hipStream_t)stream;
+  if (fold_w) return launch_conv<128, 64, 32, 64, 3, true>(p, st);
+  if (g_force_cfg >= 0) return launch_cfg(g_force_cfg, p, st);
+  const long long Mp = plan_rows(p.M);
+  if (ws) {
+    const int S = plan_splits(p.M, Cout, p.nsteps);
+    if (S > 1 && (size_t)S * p.M * Cout * sizeof(float) <= ws_bytes) {
+      ConvParams q = p;
+      q.bias = nullptr; q.res = nullptr; q.act = FRCNN_ACT_NONE; q.y = (float*)ws; q.mask = nullptr;
+      q.kchunk = cdiv(p.nsteps, S); q.splits = S; q.gz = (long long)p.M * Cout;
+      const int rc = launch_cfg(tile_cfg_64(Cout), q, st);
+      if (rc) return rc;
+      const long long total = (long long)p.M * Cout;
+      hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)min((long long)2048, (total + 255) / 256)), dim3(256), 0, st, (const float*)ws, S,
+                         p.M, Cout, bias_d, residual_d, p.res_stride, OH, OW, RH, RW, act, mask_d, y_d);
+      LAUNCH_CHECK();
+      return FRCNN_OK;
+    }
+  }
+  if (stride == 1 && KH == 1 && KW == 1 && (!residual_d || p.res_stride == 1)) {
+    int rc = FRCNN_E_UNSUPPORTED;
+    if (short_k_stream(Mp, Cout, p.nsteps, 1)) rc = launch_cfg(STREAM_64x128, p, st);
+    else if (g_stream && p.nsteps <= 8 && Cout == 64 && (Mp + 127) / 128 >= 512) rc = launch_cfg(STREAM_128x64, p, st);   // conv2_x's 64-wide 1x1
+    if (rc != FRCNN_E_UNSUPPORTED) return rc;
+  }
+  const int cfg = tile_cfg(Mp, Cout, p.nsteps, 1);
+  if (cfg != tile_cfg_64(Cout)) {
+    if (g_stagger > 0 && tiles_128(Mp, Cout, 1) >= 1024) {
+      p.stagger = (int)min((long long)p.nsteps * 8192 * g_stagger / 8, (long long)1 << 30);
+      p.stagger_slots = 2;
+    }
+  } else if (g_stagger > 0 && (g_stagger & 16) && Cout > 32 && (long long)cdiv(p.M, 64) * cdiv(Cout, 64) >= 1280) {
+    p.stagger = p.nsteps * 1024;                         // 64x64 tiles: 5 workgroups per CU (32 KB LDS), one fifth of a tile apart
+    p.stagger_slots = 5;
+  }
+  return launch_cfg(cfg, p, st);
+}
 
 extern "C" int frcnn_conv2d_nhwc(const float* x_d, int N, int H, int W, int Cin, const float* w_d, const float* bias_d,
                                  const float* residual_d, int RH, int RW, int res_stride, float* y_d, int OH, int OW,
@@ -810,120 +846,28 @@ extern "C" int frcnn_conv2d_nhwc_masked_ws(const float* x_d, int N, int H, int W
                      pad_left, act, 0, ws, ws_bytes, mask_d, stream);
 }
 
-static int conv2d_impl(const float* x_d, int N, int H, int W, int Cin, const float* w_d, const float* bias_d,
-                       const float* residual_d, int RH, int RW, int res_stride, float* y_d, int OH, int OW, int Cout, int KH, int KW,
-                       int stride, int pad_top, int pad_left, int act, int fold_w, void* ws, size_t ws_bytes, const float* mask_d,
-                       void* stream) {
-  if (!x_d || !w_d || !y_d) return FRCNN_E_ARG;
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || OH <= 0 || OW <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0)
-    return FRCNN_E_ARG;
-  if (act < 0 || act > 2) return FRCNN_E_ARG;
-  if (residual_d && (res_stride < 1 || RH < (OH - 1) * res_stride + 1 || RW < (OW - 1) * res_stride + 1)) return FRCNN_E_ARG;
-  if (fold_w) {
-    if (Cin != 4 || KW > 8) return FRCNN_E_UNSUPPORTED;
-  } else if (Cin % 32) {
-    return FRCNN_E_UNSUPPORTED;
-  }
-  if ((long long)N * H * W * Cin >= (1ll << 31) || (long long)N * OH * OW >= (1ll << 31) / 4) return FRCNN_E_UNSUPPORTED;
-  ConvParams p;
-  p.x = x_d; p.w = w_d; p.bias = bias_d; p.res = residual_d; p.y = y_d; p.mask = mask_d;
-  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout; p.KH = KH; p.KW = fold_w ? 1 : KW;
-  p.stride = stride; p.pad_top = pad_top; p.pad_left = pad_left; p.act = act;
-  p.RH = RH; p.RW = RW; p.res_stride = residual_d ? res_stride : 1;
-  p.M = N * OH * OW;
-  p.Ktot = fold_w ? KH * 32 : KH * KW * Cin;
-  p.nsteps = fold_w ? KH : KH * KW * (Cin / 32);
-  p.mtiles = p.ntiles = 0;
-  p.gx = p.gw = p.gy = p.gz = 0;
-  p.batch = 1;
-  p.splits = 1; p.kchunk = p.nsteps;
-  p.stagger = 0; p.stagger_slots = 0;
-  p.dbg = g_dbg;
-  hipStream_t st = (hipStream_t)stream;
-  if (fold_w) return launch_conv<128, 64, 32, 64, 3, true>(p, st);
-  if (g_force_cfg >= 100) return launch_stream_cfg(g_force_cfg, p, st);
-  if (g_force_cfg >= 0) return launch_cfg(g_force_cfg, p, st);
-  if (ws) {
-    const int S = plan_splits(p.M, Cout, p.nsteps);
-    if (S > 1 && (size_t)S * p.M * Cout * sizeof(float) <= ws_bytes) {
-      ConvParams q = p;
-      q.bias = nullptr; q.res = nullptr; q.act = FRCNN_ACT_NONE; q.y = (float*)ws; q.mask = nullptr;
-      q.kchunk = cdiv(p.nsteps, S); q.splits = S; q.gz = (long long)p.M * Cout;
-      const int rc = launch_cfg(Cout > 32 ? 15 : 4, q, st);
-      if (rc) return rc;
-      const long long total = (long long)p.M * Cout;
-      hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)min((long long)2048, (total + 255) / 256)), dim3(256), 0, st, (const float*)ws, S,
-                         p.M, Cout, bias_d, residual_d, p.res_stride, OH, OW, RH, RW, act, mask_d, y_d);
-      LAUNCH_CHECK();
-      return FRCNN_OK;
-    }
-  }
-  // Tile choice, from the measured sweep (profiles/r01_conv_tile_sweep.txt).  f32 MFMA needs few
-  // bytes per FLOP, so the limiter is never LDS or HBM but (a) how many of the 1024 SIMDs get a wave
-  // and (b) the per-slab barrier/ds_read overhead: 128x128 tiles with 8 waves (2 accumulators each)
-  // for the per-RoI tail (M = 14700), 64x64 tiles with a shallow ring (32 KB LDS -> up to 5
-  // workgroups per CU) for the 38x63 / 75x125 / 150x250 feature maps.
-  // Short-K pointwise convolutions (bottleneck conv3: K = Cin <= 256 into a 4x wider output + residual): a tile is only <= 8 slabs
-  // (<= 128 MFMAs per wave), so per-tile launch / prologue / LDS-staged epilogue cost as much as the multiply -> resident
-  // streaming workers with register epilogues (profiles/r02_h_stream_sweep.txt: 64.5 -> 51 us on 9576 x 1024 x 256).
-  // Which kernel / tile configuration: the configurations do not all add in the same order (8-wave tiles keep two accumulators per
-  // sub-tile), so like the split-K plan the choice follows the PLANNED rows (key 8), not the rows of this particular launch.
-  const long long Mp = plan_rows(p.M);
-  if (g_stream && p.nsteps <= 8 && stride == 1 && KH == 1 && KW == 1 && (!residual_d || p.res_stride == 1)) {
-    if (Cout % 128 == 0 && (Mp + 63) / 64 * (Cout / 128) >= 512) {
-      const int rc = launch_stream_cfg(108, p, st);
-      if (rc != FRCNN_E_UNSUPPORTED) return rc;
-    } else if (Cout == 64 && (Mp + 127) / 128 >= 512) {
-      const int rc = launch_stream_cfg(106, p, st);
-      if (rc != FRCNN_E_UNSUPPORTED) return rc;
-    }
-  }
-  const long long big = (Mp + 127) / 128 * cdiv(Cout, 128);
-  if (Cout >= 96 && big >= 384 && p.nsteps >= 8) {
-    // a 128x128 tile keeps each SIMD's matrix pipe busy for nsteps * 64 MFMAs * 64 cycles; two workgroups share a CU
-    if (g_stagger > 0 && big >= 1024) {
-      p.stagger = (int)min((long long)p.nsteps * 8192 * g_stagger / 8, (long long)1 << 30);
-      p.stagger_slots = 2;
-    }
-    return launch_cfg(Cout >= 1024 ? 21 : 20, p, st);   // reads-first; 8 waves help the residual epilogue
-  }
-  if (g_stagger > 0 && (g_stagger & 16) && Cout > 32 && (long long)cdiv(p.M, 64) * cdiv(Cout, 64) >= 1280) {
-    p.stagger = p.nsteps * 1024;                         // 64x64 tiles: 5 workgroups per CU (32 KB LDS), one fifth of a tile apart
-    p.stagger_slots = 5;
-  }
-  if (Cout > 32) return launch_cfg(15, p, st);
-  return launch_cfg(4, p, st);
-}
-
 // G independent "NT" GEMMs in one launch: y[g][m][n] = sum_k x[g][m][k] * w[g][n][k]  (f32 MFMA, same kernel, grid.y = g).
 // Used by the Winograd path (16 transformed positions).  K % 32 == 0.
 extern "C" int frcnn_gemm_batched_nt(const float* x_d, const float* w_d, float* y_d, int G, int M, int N, int K, void* stream) {
   if (!x_d || !w_d || !y_d || G <= 0 || M <= 0 || N <= 0 || K <= 0) return FRCNN_E_ARG;
   if (K % 32 || G > 65535) return FRCNN_E_UNSUPPORTED;
-  ConvParams p;
-  p.x = x_d; p.w = w_d; p.bias = nullptr; p.res = nullptr; p.y = y_d; p.mask = nullptr;
-  p.N = 1; p.H = 1; p.W = M; p.Cin = K; p.OH = 1; p.OW = M; p.Cout = N; p.KH = 1; p.KW = 1;
-  p.stride = 1; p.pad_top = 0; p.pad_left = 0; p.act = FRCNN_ACT_NONE;
-  p.RH = p.RW = 0; p.res_stride = 1;
-  p.M = M; p.Ktot = K; p.nsteps = K / 32; p.mtiles = p.ntiles = 0;
-  p.gx = (long long)M * K; p.gw = (long long)N * K; p.gy = (long long)M * N; p.gz = 0;
-  p.dbg = 0;
+  ConvParams p = conv_params();
+  p.x = x_d; p.w = w_d; p.y = y_d;
+  p.N = 1; p.H = 1; p.W = M; p.Cin = K; p.OH = 1; p.OW = M; p.Cout = N;
+  p.M = M; p.Ktot = K; p.nsteps = p.kchunk = K / 32;
+  p.gx = (long long)M * K; p.gw = (long long)N * K; p.gy = (long long)M * N;
   p.batch = G;
-  p.splits = 1; p.kchunk = p.nsteps;
-  p.stagger = 0; p.stagger_slots = 0;
-  const long long Mp = plan_rows(M);                            // key 8: configuration by the planned rows (see conv2d_impl)
-  const long long big = (Mp + 127) / 128 * cdiv(N, 128) * G;
-  if (g_force_cfg >= 100) return launch_stream_cfg(g_force_cfg, p, (hipStream_t)stream);
-  if (g_force_cfg >= 0) return launch_cfg(g_force_cfg, p, (hipStream_t)stream);
-  if (g_stream && p.nsteps <= 8 && N % 128 == 0 && (Mp + 63) / 64 * (N / 128) * G >= 512) {      // short-K batched products
-    const int rc = launch_stream_cfg(108, p, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (g_force_cfg >= 0) return launch_cfg(g_force_cfg, p, st);
+  const long long Mp = plan_rows(M);                            // key 8: configuration by the planned rows (see tile_cfg)
+  if (short_k_stream(Mp, N, p.nsteps, G)) {
+    const int rc = launch_cfg(STREAM_64x128, p, st);
     if (rc != FRCNN_E_UNSUPPORTED) return rc;
   }
   // 128-row tiles only when they waste at most a quarter of their rows: 160 Winograd tiles of one 38 x 63 image would be 2 x 128 (the RPN
   // 3x3's data gradient, N = 1024: 350 us in 128 x 128 tiles, profiles/r04_ak_*), 64-row tiles cover them with 3 x 64
   const bool waste = (Mp + 127) / 128 * 128 * 4 > Mp * 5;
-  return (N >= 96 && big >= 384 && p.nsteps >= 8 && !waste) ? launch_cfg(N >= 1024 ? 21 : 20, p, (hipStream_t)stream)
-                                                           : launch_cfg(N > 32 ? 15 : 4, p, (hipStream_t)stream);
+  return launch_cfg(waste ? tile_cfg_64(N) : tile_cfg(Mp, N, p.nsteps, G), p, st);
 }
 
 // HOST: HWIO -> [Cout][KH][KW][Cin] with optional per-output-channel scale (folded frozen BN).

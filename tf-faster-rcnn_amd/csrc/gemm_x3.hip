@@ -23,9 +23,9 @@
 // with equal n mod 4 differ in (n >> 2) & 3 -- conflict-free (round 2 used (n >> 1) & 3: two-way conflicts, SQ_LDS_BANK_CONFLICT =
 // half of SQ_LDS_IDX_ACTIVE, profiles/r03_i_pmc_gemm_h2.txt).
 #include "common.h"
+#include "mfma_f32.h"
 #include <mutex>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 struct GemmX3Params {
@@ -33,21 +33,6 @@ struct GemmX3Params {
   int M, N, K, nsteps, mtiles, ntiles, batch, act;
   long long gx, gwp, gy;               // per batch entry: elements of x / bf16 elements of wp (= 3*N*K) / elements of y
 };
-
-#define LDS_AS __attribute__((address_space(3)))
-
-__device__ __forceinline__ void x3_glds16(const void* gsrc, unsigned lds_base) {       // see conv_igemm.hip: glds16
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
 
 // exact split of 8 consecutive k values (two float4) into three bf16x8 operands, every piece rounded to nearest-even
 // (v_cvt_pk_bf16_f32): h = bf16(x), m = bf16(x - h), l = x - h - m.  Both subtractions are exact in f32 and l has at most 8
@@ -111,8 +96,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   const unsigned lds0 = (unsigned)(size_t)(LDS_AS char*)smem;
   auto issue_one = [&](int buf, int t) {
     const unsigned sb = lds0 + (unsigned)(buf * STAGE);
-    if (t < LA) x3_glds16((const char*)ia + a_lane[t], __builtin_amdgcn_readfirstlane(sb + (wave * LA + t) * 1024));
-    else x3_glds16(ib + b_lane[t - LA], __builtin_amdgcn_readfirstlane(sb + A_BYTES + (wave * LB + (t - LA)) * 1024));
+    if (t < LA) glds16((const char*)ia + a_lane[t], __builtin_amdgcn_readfirstlane(sb + (wave * LA + t) * 1024));
+    else glds16(ib + b_lane[t - LA], __builtin_amdgcn_readfirstlane(sb + A_BYTES + (wave * LB + (t - LA)) * 1024));
   };
   auto advance_k = [&]() { ia += 32; ib += 64; };
   auto issue_slab = [&](int buf) {
@@ -224,7 +209,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   issue_slab(0);
   int cur = 0, step = 0;
   for (;;) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     const bool last = step + 1 == p.nsteps;
     int next = tile;
@@ -240,7 +225,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     zero_acc();
     step = 0; tile = next; c_bm0 = i_bm0; c_bn0 = i_bn0; c_g = i_g;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 }
 
 // W [G][N][K] f32 -> planes [G][3][N][K] bf16 (h, m, l rounded to nearest): once per filter

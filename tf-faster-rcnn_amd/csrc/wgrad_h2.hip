@@ -22,9 +22,9 @@
 // per slab: the maxima buffers alternate, so the next slab's ds_max needs no barrier after this slab's fragment reads).
 // 32 KB (BT = 64) / 64 KB (BT = 128) of LDS per workgroup, >= 2 workgroups per CU: the others' MFMAs cover this one's split phase.
 #include "h2_common.h"
+#include "mfma_f32.h"
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 struct WgradH2Params {

@@ -17,9 +17,8 @@
 // is XOR-ed with 32 on odd k rows (applied to the global source chunk and to the fragment column) so that the two k rows of one
 // fragment read sit in different bank halves.
 #include "common.h"
+#include "mfma_f32.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ float4 g_wgrad_zero[32];     // 512 zero bytes: the source of padding taps and of rows past M
 
@@ -32,24 +31,6 @@ struct WgradParams {
   long long gz;                                     // Cout * Kf
 };
 
-#define LDS_AS __attribute__((address_space(3)))
-
-template <int N>
-__device__ __forceinline__ void wg_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// 64 lanes x 16 B, per-lane global source -> LDS [lds_base, +1 KiB) lane-linear (see conv_igemm.hip glds16 for why this is asm)
-__device__ __forceinline__ void wg_glds16(const float* gsrc, unsigned lds_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_base)
-      : "memory");
-}
 
 template <int BT, int NS>
 __global__ __launch_bounds__(256) void k_wgrad_tn(const WgradParams p) {
@@ -89,7 +70,7 @@ __global__ __launch_bounds__(256) void k_wgrad_tn(const WgradParams p) {
     for (int t = 0; t < LA; ++t) {
       const int m = m_next + a_row[t];
       const float* src = m < p.M ? p.gy + (size_t)m * p.Cout + co0 + q4[t] : zero;
-      wg_glds16(src, __builtin_amdgcn_readfirstlane(sb + (wave * LA + t) * 1024));
+      glds16(src, __builtin_amdgcn_readfirstlane(sb + (wave * LA + t) * 1024));
     }
 #pragma unroll
     for (int t = 0; t < LA; ++t) {
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(256) void k_wgrad_tn(const WgradParams p) {
             src = p.x + ((size_t)(img * p.H + ih) * p.W + iw) * p.Cin + c0 + q4[t];
         }
       }
-      wg_glds16(src, __builtin_amdgcn_readfirstlane(sb + 32 * BT * 4 + (wave * LA + t) * 1024));
+      glds16(src, __builtin_amdgcn_readfirstlane(sb + 32 * BT * 4 + (wave * LA + t) * 1024));
     }
     m_next += 32;
   };
@@ -135,8 +116,8 @@ __global__ __launch_bounds__(256) void k_wgrad_tn(const WgradParams p) {
 
   auto slab = [&](auto more_c, int step) {
     constexpr bool MORE = decltype(more_c)::value;
-    if (MORE || step + P <= nloc) wg_wait_vmcnt<(P - 1) * G>();
-    else wg_wait_vmcnt<0>();
+    if (MORE || step + P <= nloc) wait_vmcnt<(P - 1) * G>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     const float* sb = smem + (step % NS) * SLAB;
     if (MORE) issue_slab((step + P) % NS);

@@ -152,7 +152,10 @@ def test_tensor_operations_of_a_step_are_replayed_whatever_they_return():
 
 def test_arena_hands_out_the_same_tensors_every_step_and_only_while_active():
     class Sess(object):
-        buffers, device = {}, torch.device("cpu")
+        buffers, device, picking, picked_streams = {}, torch.device("cpu"), False, None
+
+        def _store(self):
+            return self.buffers
     a = replay.Arena(Sess(), "t")
     ops.arena = a
     try:
@@ -212,7 +215,10 @@ class _Prepared(object):
 class _Sess(object):
     def __init__(self):
         self.graphs, self.buffers, self.device, self.prepared = {}, {}, torch.device("cpu"), _Prepared()
-        self.derived_gen = 0
+        self.derived_gen, self.picking, self.picked_streams = 0, False, None
+
+    def _store(self):
+        return self.buffers
 
     def derived_generation(self):
         return (self.derived_gen, self.prepared.gen)
@@ -369,7 +375,7 @@ def test_evicting_the_entry_that_runs_the_stream_search_ends_the_search(monkeypa
         a, b, c = (dict(shape=(1, 4, w, 4), G=3) for w in (6, 8, 10))
         for _ in range(3):
             net.train_step_async(sess, a, op)                   # eager, recorded, first replay: the search starts on shape a
-        assert sess.picking and getattr(sess, "picked_streams", None) is None
+        assert sess.picking and sess.picked_streams is None
         net.train_step_async(sess, b, op)
         net.train_step_async(sess, b, op)
         assert sess.picking                                     # (shape a's entry is still there)

@@ -4,26 +4,27 @@ shape owns static buffers, so the session keeps them per shape and least-recentl
 a buffer request lands in, what an eviction drops (buffers, the captured graph, recorded steps that address the buffers, a running
 stream search), that weight-shaped buffers stay with the session, and that scratch follows the scope.  The device behaviour (memory
 bounded over 64 shapes, bit-identical detections) is tests/test_streaming_shapes_gpu.py."""
-import collections
-
 import pytest
 import torch
 
-from frcnn_hip import ops
-from frcnn_hip.runtime import PreparedFilters, Session, VariableStore
+from frcnn_hip import ops, replay
+from frcnn_hip.runtime import Session
+
+
+def _host_session():
+    s = Session.__new__(Session)                     # (Session() needs a GPU; the bookkeeping does not)
+    s._init_host(torch.device("cpu"), 3)
+    return s
 
 
 @pytest.fixture
 def sess(monkeypatch):
-    s = Session.__new__(Session)                     # (Session() needs a GPU; the bookkeeping does not)
-    VariableStore.__init__(s, 3)
-    s.device = torch.device("cpu")
-    s.buffers, s.scopes, s.scope_group = {}, collections.OrderedDict(), {}
-    s.prepared = PreparedFilters(s.device)
+    s = _host_session()
     s.synced = []
     monkeypatch.setattr(torch.cuda, "synchronize", lambda device=None: s.synced.append(device))
+    assert ops.scope_depth() == 0
     yield s
-    ops.scope_store = None
+    del ops._scope_stack[1:]
 
 
 def test_requests_land_in_the_active_scope_and_the_session_otherwise(sess):
@@ -37,7 +38,7 @@ def test_requests_land_in_the_active_scope_and_the_session_otherwise(sess):
         assert ops.workspace(50, sess.device, "x") is ws
         big = ops.workspace(200, sess.device, "x")                                   # grows: the old one is retired INTO the scope
         assert big is not ws and sess.scopes["A"][("ws_retired",)] == [ws]
-    assert ops.scope_store is None
+    assert ops.scope_depth() == 0
     assert set(sess.buffers) == {("w", (4,), torch.float32)}
     assert ("act", (8,), torch.float32) in sess.scopes["A"] and sess.scope_bytes("A") >= 8 * 4 + 4 * 4 + 200
     with sess.shape_scope("A", group="t", cap=2):
@@ -87,3 +88,83 @@ def test_prepared_filter_images_are_session_wide_even_when_first_built_inside_a_
         pass
     assert "A" not in sess.scopes and out is sess.buffers[("bwd/wflip/conv", (3, 3), torch.float32)]
     assert fn() is out                                                               # what a later refresh() (outside any scope) writes: the same tensor
+
+
+def test_another_sessions_requests_never_land_in_the_entered_scope(sess):
+    """Session B asks for static buffers while A's scope is entered: they are B's (its captured graphs live in B.graphs, which A's eviction
+    never drops), and B does not find A's tensors."""
+    A, B = sess, _host_session()
+    arena = replay.Arena(B, "t")
+    with A.shape_scope("k", group="t", cap=2):
+        b, h, t = B.buf("act", (8,)), B._store(), arena.take((2, 3), torch.float32, None)
+        a = A.buf("act", (8,))
+        assert h is B.buffers                                                        # (where h2_buf registers its operand planes)
+        assert B.buffers[("act", (8,), torch.float32)] is b and B.buffers[("arena", "t", 0, (2, 3), torch.float32)] is t
+        assert A.scopes["k"] == {("act", (8,), torch.float32): a} and a is not b and A._store() is A.scopes["k"]
+        assert B.find_buf("act", (8,)) is b and A.find_buf("act", (8,)) is a
+        with pytest.raises(KeyError):
+            B.find_buf("only_a", A.buf("only_a", (4,)).shape)                        # same name and shape, A's: not B's to find
+    assert B.scopes == {} and A.buffers == {} and ops.scope_depth() == 0
+
+
+def test_h2_operand_planes_follow_the_owner_too(sess, monkeypatch):
+    A, B = sess, _host_session()
+    monkeypatch.setattr(ops.H2, "empty", staticmethod(lambda rows, K, device: ("planes", rows, K)))
+    with A.shape_scope("k", group="t", cap=2):
+        assert B.h2_buf("x", 4, 128) is B.buffers[("h2", "x", 4, 128)] and A.h2_buf("x", 4, 128) is A.scopes["k"][("h2", "x", 4, 128)]
+    assert ("h2", "x", 4, 128) not in A.buffers and B.scopes == {}
+
+
+def test_each_session_owns_the_scope_it_entered(sess):
+    A, B = sess, _host_session()
+    with A.shape_scope("k", group="t", cap=2):
+        with B.shape_scope("kb", group="t", cap=2):
+            assert ops.scope_depth() == 2
+            b, a = B.buf("act", (8,)), A.buf("act", (8,))
+            ws = ops.workspace(64, B.device, "x")                                    # scratch follows the innermost entered scope
+        a2 = A.buf("act2", (8,))
+    assert ops.scope_depth() == 0
+    assert B.scopes["kb"] == {("act", (8,), torch.float32): b, ("ws", "cpu", "x", ops.ws_scope): ws} and B.buffers == {}
+    assert A.buffers == {("act", (8,), torch.float32): a} and A.scopes["k"] == {("act2", (8,), torch.float32): a2}
+
+
+def test_an_entered_scope_is_never_evicted(sess):
+    with sess.shape_scope("A", group="t", cap=1):
+        a = sess.buf("act", (8,))
+        with sess.shape_scope("B", group="t", cap=1):                                # over the cap, but A is entered: the group exceeds it
+            assert list(sess.scopes) == ["A", "B"] and sess.synced == []
+            assert sess.buf("act", (8,)) is not a
+            with sess.shape_scope("A", group="t", cap=1):                            # re-entering an entered key: LRU order, nothing else
+                assert sess.buf("act", (8,)) is a and list(sess.scopes) == ["B", "A"]
+        assert sess.scopes["A"][("act", (8,), torch.float32)] is a and sess.buf("act", (8,)) is a
+    assert sess.synced == [] and set(sess.scopes) == {"A", "B"} and ops.scope_depth() == 0
+    with sess.shape_scope("C", group="t", cap=1):                                    # nothing entered any more: down to the cap, one synchronize
+        assert list(sess.scopes) == ["C"] and len(sess.synced) == 1
+    with sess.shape_scope("D", group="t", cap=2):
+        with sess.shape_scope("E", group="t", cap=2):                                # the victims are the oldest scopes that are NOT entered
+            assert list(sess.scopes) == ["D", "E"] and len(sess.synced) == 2         # (C went, D stayed)
+
+
+def test_an_exception_leaves_the_scope_stack_where_it_was(sess):
+    with sess.shape_scope("A", group="t", cap=2):
+        with pytest.raises(ValueError):
+            with sess.shape_scope("B", group="t", cap=2):
+                raise ValueError("inside a scope")
+        assert ops.scope_depth() == 1 and sess._store() is sess.scopes["A"]
+        with pytest.raises(ValueError):
+            with ops.unscoped():
+                assert sess._store() is sess.buffers
+                raise ValueError("inside unscoped()")
+        assert ops.scope_depth() == 1 and sess._store() is sess.scopes["A"]
+    assert ops.scope_depth() == 0
+
+
+def test_init_host_declares_every_field_the_host_code_reads_on_a_session(sess):
+    """runtime.py, replay.py and lib/nets/network.py read these as plain attributes: a misspelt name raises instead of becoming a default."""
+    for name in ("variables", "packed", "x3", "h2", "h2_spread", "conv_info", "graphs", "seed", "device_filters_moved", "derived_gen", "device",
+                 "buffers", "scopes", "scope_group", "poison_new_buffers", "scope_cap_override", "profile", "flops_last_forward", "flops_by_pipe",
+                 "prepared", "picking", "picked_streams", "pick_log"):
+        assert name in vars(sess), name
+    assert sess.picking is False and sess.picked_streams is None and sess.pick_log == [] and isinstance(sess.graphs, dict)
+    assert isinstance(sess.poison_new_buffers, bool) and (sess.scope_cap_override is None or sess.scope_cap_override >= 1)
+    assert sess.prepared.device == sess.device and not hasattr(sess, "stream")       # the stream is the GPU part (Session.__init__)

@@ -175,6 +175,62 @@ def test_a_graph_follows_the_image_wherever_the_caller_staged_it(dev):
         cfg.TEST.RPN_POST_NMS_TOP_N = old
 
 
+def _addresses(store):
+    """device addresses of everything a buffer store holds: tensors, operand planes (ops.H2), lists of retired scratch"""
+    out = set()
+
+    def walk(v):
+        if torch.is_tensor(v):
+            out.add(v.data_ptr())
+        elif isinstance(v, (tuple, list)):
+            for x in v:
+                walk(x)
+        else:
+            for a in ("planes", "inv"):
+                if hasattr(v, a):
+                    walk(getattr(v, a))
+    for v in store.values():
+        walk(v)
+    return out
+
+
+def test_a_session_that_runs_inside_another_sessions_scope_keeps_its_own_buffers(dev):
+    """Session B captures a shape while session A's scope is entered (several sessions share a process: bench.py, this suite).  What B
+    allocated is B's: dropping A's scope frees nothing B's graph addresses, so after A has run another shape out of the freed blocks, B's
+    replay still gives the bits of a fresh session."""
+    from model.config import cfg
+    old = cfg.TEST.RPN_POST_NMS_TOP_N
+    cfg.TEST.RPN_POST_NMS_TOP_N = 48
+    try:
+        (sa, na), (sb, nb) = _net(dev, "own_a"), _net(dev, "own_b")
+        (H1, W1), (H2, W2) = (112, 144), (120, 160)
+        img1, info1 = _image(H1, W1, 1), np.array([H1, W1, 1.0], dtype=np.float32)
+        key_a = na.graph_key((1, H2, W2, 4), (H2, W2))
+        with na.shape_scope(sa, (1, H2, W2, 4), (H2, W2)):                           # A's scope of size 2 is entered ...
+            mine = sa.buf("own_a/probe", (1 << 16,))
+            nb.test_image(sb, img1, info1)                                           # ... while B captures size 1
+            theirs = sb.buf("own_b/probe", (16,))
+        assert sb.buffers[("own_b/probe", (16,), torch.float32)] is theirs and list(sa.scopes[key_a].values()) == [mine]
+        torch.cuda.synchronize()
+        dropped = _addresses(sa.scopes[key_a])
+        kept = set().union(*[_addresses(st) for st in list(sb.scopes.values()) + [sb.buffers]])
+        assert dropped and len(kept) > 50 and not (dropped & kept)                   # nothing of B's lived in the scope that goes
+        del mine
+        assert sa.drop_scope(key_a)
+        na.test_image(sa, _image(H2, W2, 2), np.array([H2, W2, 1.0], dtype=np.float32))      # A runs size 2 out of the freed blocks
+        torch.cuda.synchronize()
+        assert len([k for k in sb.graphs if k[0] == "own_b"]) == 1
+        again = nb.test_image(sb, img1, info1)                                       # B replays its graph of size 1
+        s3, n3 = _net(dev, "own_fresh")
+        want = n3.test_image(s3, img1, info1)
+        assert len(again) == 4 and all(torch.equal(torch.from_numpy(x), torch.from_numpy(y)) for x, y in zip(again, want))
+        assert again[3].shape[0] > 0
+        for s in (sa, sb, s3):
+            s.close()
+    finally:
+        cfg.TEST.RPN_POST_NMS_TOP_N = old
+
+
 def test_training_over_changing_image_shapes_stays_bounded_and_reproducible(dev):
     """A roidb's images differ in size from step to step (lib/roi_data_layer/layer.py:80-93, lib/model/train_val.py:236-260).  With two
     shapes cached (cfg.HIP.TRAIN_CACHE_SHAPES = 2) a run over five shapes evicts and rebuilds scopes and recordings all the time; it must

@@ -13,28 +13,32 @@ import frcnn_hip as _binding
 from . import ACT_NONE, NMS_RULE_CPU, call, lib
 
 _ws_cache = {}
-_ws_retired = []
 ws_scope = "default"     # set by callers that run several independent chains concurrently (one scope per stream)
 
-# The per-SHAPE buffer set of the build that is running (Session.shape_scope; None outside one).  Everything whose size follows the image --
-# named activation buffers, operand planes, arena results, scratch -- is registered there while it is set, so that evicting a shape's
-# captured graph / recorded step frees (returns to torch's size-class pools) exactly what that shape needed.  Weight-shaped buffers stay
-# session-wide: their producers run under `unscoped()`.
-scope_store = None
+# The entered buffer scopes, innermost last: (owner, key, store) -- Session.shape_scope pushes (the session, the shape's key, that shape's
+# buffer dict), see the comment there.  The bottom entry, and unscoped()'s, is "no scope".  One stack per process, not per thread, like
+# stream_pin, arena, ws_scope and frcnn_hip.recorder: a step is single-threaded by design.
+_scope_stack = [(None, None, None)]
+
+
+def active_store(owner, default=None):
+    """The innermost entered scope's store if `owner` entered it (owner = None: whoever did); `default` otherwise and outside every scope."""
+    o, _, store = _scope_stack[-1]
+    return store if store is not None and (owner is None or o is owner) else default
+
+
+def scope_depth():
+    return len(_scope_stack) - 1
 
 
 class unscoped(object):
     """`with unscoped():` -- buffers allocated inside belong to the session, not to the image shape being built (filter images, solver state)."""
 
     def __enter__(self):
-        global scope_store
-        self.prev, scope_store = scope_store, None
-        return self
+        _scope_stack.append(_scope_stack[0])
 
     def __exit__(self, *exc):
-        global scope_store
-        scope_store = self.prev
-        return False
+        _scope_stack.pop()
 
 
 stream_pin = None        # a ctypes stream handle: every launch of this module goes there instead of torch's current stream (see pinned_stream)
@@ -154,14 +158,15 @@ def _chk(t, dtype=torch.float32):
 def workspace(nbytes, device, tag="default"):
     """Grow-only scratch buffer per (device, tag); never reallocated inside a captured region
     as long as the first (warm-up) call already saw the largest request."""
-    # inside a shape scope the scratch belongs to the shape (freed with it); a buffer a captured graph may still address is retired INTO the
-    # same store, i.e. lives exactly as long as that graph
-    store = _ws_cache if scope_store is None else scope_store
+    # scratch follows the INNERMOST entered scope, whoever owns it (there is no session in hand here; every Network entry point --
+    # forward_device, extract_head, detect_device, train_step_async -- enters its own session's scope before its first launch): it belongs to
+    # that shape and is freed with it; a buffer a captured graph may still address is retired INTO the same store, i.e. lives as long as it
+    store = active_store(None, _ws_cache)
     key = ("ws", str(device), tag, ws_scope)
     buf = store.get(key)
     if buf is None or buf.numel() < nbytes:
         if buf is not None:
-            (_ws_retired if scope_store is None else store.setdefault(("ws_retired",), [])).append(buf)
+            store.setdefault(("ws_retired",), []).append(buf)
         buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         store[key] = buf
     return buf

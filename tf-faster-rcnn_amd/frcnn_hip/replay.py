@@ -18,6 +18,7 @@ recorded (`patch_last`) and rewritten at replay from the step's seed counter.
 
 """
 import ctypes
+import time
 
 import torch
 
@@ -36,7 +37,7 @@ class Arena(object):
     def take(self, shape, dtype, device):
         key = ("arena", self.tag, self.n, tuple(int(s) for s in shape), dtype)
         self.n += 1
-        store = self.sess._store() if hasattr(self.sess, "_store") else self.sess.buffers      # (per image shape inside Session.shape_scope)
+        store = self.sess._store()                              # (per image shape inside Session.shape_scope)
         t = store.get(key)
         if t is None:
             t = store[key] = torch.empty(key[3], dtype=dtype, device=self.sess.device if device is None else device)
@@ -61,18 +62,13 @@ class Recording(object):
     # ---- recording ---------------------------------------------------------------------------------------------------------------------
     def slot(self, stream):
         """slot of a torch stream (helper streams register themselves at first use)"""
-        h = int(stream.cuda_stream)
-        s = self.slot_of.get(h)
-        if s is None:
-            s = self.slot_of[h] = len(self.streams)
-            self.streams.append(stream)
-        return s
+        return self._slot_of_handle(int(stream.cuda_stream), stream)
 
-    def _slot_of_handle(self, h):
+    def _slot_of_handle(self, h, stream=None):
         s = self.slot_of.get(h)
         if s is None:
             s = self.slot_of[h] = len(self.streams)
-            self.streams.append(torch.cuda.ExternalStream(h))
+            self.streams.append(torch.cuda.ExternalStream(h) if stream is None else stream)
         return s
 
     def add_call(self, fn, name, args):
@@ -184,7 +180,6 @@ class StreamPicker(object):
         return b
 
     def before_step(self, main):
-        import time
         if self.done or self.left:
             return
         while self.queue:
@@ -201,7 +196,6 @@ class StreamPicker(object):
         self.left, self.t0 = self.window, time.perf_counter()
 
     def after_step(self, main):
-        import time
         if self.done or not self.left:
             return
         self.left -= 1

@@ -24,6 +24,7 @@ class VarSpec(object):
 class VariableStore(object):
     """Host side of a session: the variables under their TF/slim names (numpy, HWIO filters, [in,out] matrices), their
     initialisation and checkpoint I/O.  No device state -- Session adds that."""
+    prepared = None                                     # (Session: the prepared-filter plan, PreparedFilters)
 
     def __init__(self, seed=3):
         self.variables = collections.OrderedDict()     # TF name -> numpy (HWIO conv, [in,out] fc)
@@ -95,16 +96,12 @@ class VariableStore(object):
         """Everything computed FROM the variables: packed device images, pre-split x3 / h2 filter planes, captured graphs and (Session)
         the prepared-filter plan whose closures hold the filter tensors -- a direct load / restore between training steps must not leave
         the data-gradient chain reading flipped / Winograd / h2 filters derived from tensors that were just dropped."""
-        self.packed.clear()
-        self.x3.clear()
-        self.h2.clear()
-        self.h2_spread.clear()
-        self.graphs.clear()
+        for d in (self.packed, self.x3, self.h2, self.h2_spread, self.graphs):
+            d.clear()
         self.derived_gen += 1
         self.device_filters_moved = False               # (the device images are rebuilt from the host variables from here on)
-        prepared = getattr(self, "prepared", None)
-        if prepared is not None:
-            prepared.invalidate()
+        if self.prepared is not None:
+            self.prepared.invalidate()
 
     def load_variables(self, values):
         for k, v in values.items():
@@ -256,9 +253,13 @@ class Session(VariableStore):
     def __init__(self, device=None, seed=3):
         if not torch.cuda.is_available():
             raise RuntimeError("frcnn_hip.Session needs a GPU: the product path has no CPU fallback")
-        VariableStore.__init__(self, seed)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._init_host(torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device), seed)
         self.stream = torch.cuda.Stream(device=self.device)
+
+    def _init_host(self, device, seed):
+        """Every field that needs no GPU, declared in one place (the CPU tests of the bookkeeping build their sessions with it)."""
+        VariableStore.__init__(self, seed)
+        self.device = device
         self.buffers = {}                               # session-wide buffers (weight-shaped, solver state, anything allocated outside a scope)
         self.scopes = collections.OrderedDict()         # shape-scope key -> {buffer key: tensor}, least recently entered first (shape_scope)
         self.scope_group = {}                           # shape-scope key -> LRU group
@@ -270,6 +271,7 @@ class Session(VariableStore):
         self.flops_last_forward = 0
         self.flops_by_pipe = None                       # dict while somebody wants the split (Session.mark)
         self.prepared = PreparedFilters(self.device)
+        self.picking, self.picked_streams, self.pick_log = False, None, []      # the once-per-session stream search (replay.StreamPicker)
 
     # ---- device-side images of the variables ----------------------------------------------------
     def to_device(self, a, dtype=torch.float32):
@@ -344,9 +346,11 @@ class Session(VariableStore):
     # ---- buffers: per session, or per image shape -------------------------------------------------------------------------------------
     # The reference's graph takes [1, None, None, 3] and test_net walks an imdb whose images all differ in size (lib/nets/network.py:386-390,
     # lib/model/test.py:138-185).  Here every distinct shape has its own static buffers (a captured hipGraph / a recorded step addresses
-    # them), so they are grouped per shape and the groups are kept least-recently-used: entering a scope beyond the group's cap drops the
-    # oldest shapes -- captured graph, activation buffers, operand planes, arena results, scratch -- back to torch's allocator, whose
-    # size-class pools hand the blocks to the next shape.  Memory is bounded by cap shapes per group, not by the imdb.
+    # them): activations, operand planes, arena results, scratch.  While a shape's scope is entered (ops._scope_stack), the requests of the
+    # session that entered it -- and of nobody else: another session's graphs are not dropped with this one's scope -- land in that shape's
+    # dict.  Scopes are kept least-recently-used per group: entering one beyond the group's cap drops the oldest with their graphs, back to
+    # torch's size-class pools and the next shape.  An ENTERED scope is never a victim (a build is registering buffers in it), so a nested
+    # scope may leave its group above the cap until the next __enter__.  Memory is bounded by cap shapes per group, not by the imdb.
     class _Scope(object):
         def __init__(self, sess, key, group, cap):
             self.sess, self.key, self.group, self.cap = sess, key, group, cap
@@ -355,9 +359,10 @@ class Session(VariableStore):
             s = self.sess
             if self.key not in s.scopes:
                 if self.cap is not None:
-                    cap = getattr(s, "scope_cap_override", None) or self.cap
+                    cap = s.scope_cap_override or self.cap
                     live = [k for k in s.scopes if s.scope_group.get(k) == self.group]
-                    drop = live[:max(0, len(live) + 1 - max(1, int(cap)))]
+                    entered = [k for o, k, _ in ops._scope_stack if o is s]
+                    drop = [k for k in live if k not in entered][:max(0, len(live) + 1 - max(1, int(cap)))]
                     if drop:
                         torch.cuda.synchronize(s.device)          # a replay of an evicted graph may still be running
                         for k in drop:
@@ -365,12 +370,13 @@ class Session(VariableStore):
                 s.scopes[self.key] = {}
                 s.scope_group[self.key] = self.group
             s.scopes.move_to_end(self.key)
-            self.prev, ops.scope_store = ops.scope_store, s.scopes[self.key]
+            self.entry = (s, self.key, s.scopes[self.key])
+            ops._scope_stack.append(self.entry)
             return self
 
         def __exit__(self, *exc):
-            ops.scope_store = self.prev
-            return False
+            assert ops._scope_stack[-1] is self.entry, "scopes exit innermost first"
+            ops._scope_stack.pop()
 
     def shape_scope(self, key, group=None, cap=None):
         """`with sess.shape_scope(key, group, cap):` -- buffers requested inside belong to `key` (an image shape's graph key / recorded-step
@@ -390,14 +396,13 @@ class Session(VariableStore):
         return self.scopes.pop(key, None) is not None
 
     def _store(self):
-        return self.buffers if ops.scope_store is None else ops.scope_store
+        return ops.active_store(self, self.buffers)
 
     def find_buf(self, name, shape, dtype=torch.float32):
-        """A named buffer wherever it lives: the active scope, the most recently entered shape scopes, the session (tests / harnesses that
-        inspect an intermediate tensor after a run; the product path asks through buf() inside the right scope)."""
+        """A named buffer wherever it lives: the active scope if it is this session's, the most recently entered shape scopes, the session
+        (tests / harnesses that inspect an intermediate tensor after a run; the product path asks through buf() inside the right scope)."""
         key = (name, tuple(shape), dtype)
-        stores = ([ops.scope_store] if ops.scope_store is not None else []) + list(reversed(self.scopes.values())) + [self.buffers]
-        for st in stores:
+        for st in [ops.active_store(self, {})] + list(reversed(self.scopes.values())) + [self.buffers]:
             if key in st:
                 return st[key]
         raise KeyError(key)
@@ -415,13 +420,13 @@ class Session(VariableStore):
 
     def buf(self, name, shape, dtype=torch.float32, zero=False):
         key = (name, tuple(shape), dtype)
-        store = self._store()
+        top = ops._scope_stack[-1]                      # ops.active_store(self, self.buffers) without the call: ~1 300 requests per eager step
+        store = top[2] if top[0] is self else self.buffers
         t = store.get(key)
         if t is None:
-            t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
-            if getattr(self, "poison_new_buffers", False) and not zero:
+            t = store[key] = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
+            if self.poison_new_buffers and not zero:
                 t.view(torch.uint8).fill_(0xFF)         # float32 / fp16 NaN, int32 -1
-            store[key] = t
         return t
 
     # ---- profiling hook: HIP events around selected launches, on the stream they run on ----------
@@ -497,7 +502,7 @@ class Session(VariableStore):
     def h2_buf(self, name, rows, K):
         """Static operand-plane buffer (ops.H2) for an activation tensor of [rows, K]."""
         key = ("h2", name, int(rows), int(K))
-        store = self._store()
+        store = ops.active_store(self, self.buffers)
         t = store.get(key)
         if t is None:
             t = store[key] = ops.H2.empty(rows, K, self.device)
@@ -531,13 +536,8 @@ class Session(VariableStore):
         torch.cuda.current_stream(self.device).synchronize()
 
     def close(self):
-        self.graphs.clear()
-        self.scopes.clear()
-        self.scope_group.clear()
-        self.buffers.clear()
-        self.packed.clear()
-        self.x3.clear()
-        self.h2.clear()
+        for d in (self.graphs, self.scopes, self.scope_group, self.buffers, self.packed, self.x3, self.h2):
+            d.clear()
 
 
 class Timer(object):

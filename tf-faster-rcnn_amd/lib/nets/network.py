@@ -44,6 +44,7 @@ class Network(object):
         self._gt_boxes = None
         self._sample_seed = 0
         self.replay_stats = dict(eager=0, recorded=0, replayed=0)      # train_step_async under cfg.HIP.TRAIN_REPLAY
+        self._replay_clock, self._train_arena, self._train_scope_key = 0, None, None     # LRU clock of the recordings, replay.Arena, the step's shape scope
         self._train_state = None
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
         self._h2_of = {}                       # activation address -> ops.H2 operand planes of that tensor (cfg.HIP.MFMA_H2)
@@ -865,8 +866,8 @@ class Network(object):
             live = [k for k in sess.graphs if isinstance(k, tuple) and k and k[0] == "train_replay"]
             if len(live) >= self.REPLAY_CAP:
                 self._drop_recording(sess, min(live, key=lambda k: sess.graphs[k]["used"]))
-            ent = sess.graphs[key] = dict(seen=0, rec=None, used=0, scope=getattr(self, "_train_scope_key", None))
-        self._replay_clock = getattr(self, "_replay_clock", 0) + 1
+            ent = sess.graphs[key] = dict(seen=0, rec=None, used=0, scope=self._train_scope_key)
+        self._replay_clock += 1
         ent["used"] = self._replay_clock
         out = sess.buf(self._tag + "/train/losses", (5,))
         rec = ent["rec"]
@@ -880,8 +881,8 @@ class Network(object):
             # which physical stream every helper slot runs on: inherited from the recording, or (cfg.HIP.TRAIN_PICK_STREAMS = pool size)
             # searched once per session by timing real steps (replay.StreamPicker) and then shared by every recording with the same slots
             pk = ent.get("picker")
-            picked = getattr(sess, "picked_streams", None)
-            if pk is None and int(cfg.HIP.TRAIN_PICK_STREAMS) > 0 and picked is None and not getattr(sess, "picking", False):
+            picked = sess.picked_streams
+            if pk is None and int(cfg.HIP.TRAIN_PICK_STREAMS) > 0 and picked is None and not sess.picking:
                 pool = [torch.cuda.Stream(device=sess.device) for _ in range(int(cfg.HIP.TRAIN_PICK_STREAMS))]
                 pk = ent["picker"] = replay.StreamPicker(rec, main, pool)
                 sess.picking = True
@@ -907,7 +908,7 @@ class Network(object):
                 if pk.done:
                     sess.picked_streams, sess.picking, sess.pick_log = list(pk.best[1:]), False, list(pk.log)
             return out.clone()
-        arena = getattr(self, "_train_arena", None)
+        arena = self._train_arena
         if arena is None or arena.sess is not sess:
             arena = self._train_arena = replay.Arena(sess, self._tag + "/train")
         arena.reset()

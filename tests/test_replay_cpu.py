@@ -237,6 +237,7 @@ class _Sess(object):
 
 class _TrainOp(object):
     lr, params, _sgd_table = 1e-3, {"w": 1}, object()
+    pending_slots, world_size, all_reduce = None, 1, None      # what Network._train_step_body reads of the handle
 
     def replay_signature(self):
         return ("sig",)
@@ -312,6 +313,29 @@ def test_train_step_goes_eager_then_recorded_then_replayed(monkeypatch):
         assert net.replay_stats == dict(eager=3, recorded=1, replayed=2)              # (the switch off: not counted, nothing replayed)
     finally:
         cfg.HIP.TRAIN_REPLAY, cfg.HIP.TRAIN_PICK_STREAMS = old
+
+
+def test_a_fresh_solver_handle_keeps_one_recording_key_from_its_first_step(monkeypatch):
+    """TrainState.replay_signature() carries the switches that Network.configure_train_op sets from cfg.HIP, so the step configures the
+    handle BEFORE it forms the recording's key: a handle straight from the constructor (switches at their defaults, which are not what
+    cfg.HIP says) is eager once, recorded at its second step and replayed from the third, under one key."""
+    from frcnn_hip.train import TrainState
+    from model.config import cfg
+    log = []
+    net, main, side, made = _stub_net(monkeypatch, log)
+    sess, op = _Sess(), TrainState(None, None)
+    op.lr, op.params, op._sgd_table = 1e-3, {"w": 1}, object()
+    fresh = op.replay_signature()
+    old = (cfg.HIP.TRAIN_REPLAY, cfg.HIP.TRAIN_PICK_STREAMS)
+    cfg.HIP.TRAIN_REPLAY, cfg.HIP.TRAIN_PICK_STREAMS = True, 0
+    try:
+        for _ in range(3):
+            net.train_step_async(sess, dict(shape=(1, 4, 6, 4), G=3), op)
+    finally:
+        cfg.HIP.TRAIN_REPLAY, cfg.HIP.TRAIN_PICK_STREAMS = old
+    assert op.replay_signature() != fresh                       # (the case is not vacuous: cfg.HIP moved the switches)
+    assert net.replay_stats == dict(eager=1, recorded=1, replayed=1)
+    assert len([k for k in sess.graphs if k[0] == "train_replay"]) == 1
 
 
 def test_recording_is_dropped_when_the_derived_filter_set_grows(monkeypatch):

@@ -254,6 +254,9 @@ class Net(object):
         self.params, self._tape, self._requires_grad = {}, [], set()
         self.autograd_w = {}
 
+    def weight_decay_for(self, scope):
+        return None
+
     def conv(self, sess, x, scope, cout, k, stride=1, act=ACT_RELU, residual=None, res_stride=1, x_ref=None, res_ref=None):
         cin = x.shape[3]
         w = (torch.randn((cout, k, k, cin), generator=self.g) * (1.5 / (k * np.sqrt(cin)))).float()
@@ -273,7 +276,7 @@ class Net(object):
         self._requires_grad.add(y.data_ptr())
         grad_w = torch.zeros_like(w)
         self.params[scope] = types.SimpleNamespace(scope=scope, K=w[0].numel(), bias=None, grad_w=grad_w, grad_b=None, w=w, wf=w, scale=None,
-                                                   acc_w=torch.zeros_like(w), acc_b=None)
+                                                   acc_w=torch.zeros_like(w), acc_b=None, dw=False)
         return y, y_ref
 
 
@@ -314,13 +317,12 @@ def run_sweep(monkeypatch, fuse, pipe, wino, h2_train, seed=0):
     monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
     sess = FakeSession()
     net, seeds = build(sess, seed)
-    ts = train.TrainState.__new__(train.TrainState)
-    ts.sess, ts.net, ts.params, ts.flat = sess, net, net.params, None
-    ts._wgrad_events = None
+    ts = train.TrainState(sess, net)
+    ts.params = net.params                                   # (the stand-in for build())
     ts.fuse_chain, ts.pipe_dgrads = fuse, pipe
     ts.winograd = (4, 64, True) if wino else None
     ts.h2_train = h2_train
-    ts.wgrad_stream, ts.wgrad_tn, ts.wgrad_h2, ts.prep_stream = 2, True, True, False
+    ts.wgrad_stream, ts.wgrad_h2, ts.prep_stream = 2, True, False
     ts._sweep(seeds, FakeStream())
     return net, ops.log
 
@@ -368,12 +370,10 @@ def run_steps(monkeypatch, in_sweep, steps=3, chunk=3):
     monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
     sess = FakeSession()
     net, seeds = build(sess, 5)
-    ts = train.TrainState.__new__(train.TrainState)
-    ts.sess, ts.net, ts.params, ts.flat = sess, net, net.params, None
-    ts._wgrad_events, ts.reg_scopes = None, []
-    ts.momentum, ts.weight_decay, ts.double_bias, ts.bias_decay = 0.9, 1e-4, False, False
-    ts.fuse_chain, ts.pipe_dgrads, ts.winograd, ts.h2_train = True, True, (4, 64, True), 1
-    ts.wgrad_stream, ts.wgrad_tn, ts.wgrad_h2, ts.prep_stream = 2, True, True, False
+    ts = train.TrainState(sess, net, momentum=0.9, weight_decay=1e-4)
+    ts.params = net.params
+    ts.winograd, ts.h2_train = (4, 64, True), 1
+    ts.wgrad_stream, ts.wgrad_h2, ts.prep_stream = 2, True, False
     ts.solver_in_sweep, ts.SOLVER_CHUNK, ts.lr = in_sweep, chunk, 1e-4
     order = []
     for _ in range(steps):
@@ -453,12 +453,10 @@ def run_dp_steps(monkeypatch, in_sweep, steps=3, chunk=3, bucket=40000):
         n = p.grad_w.numel()
         p.grad_w = flat[off:off + n].view(p.grad_w.shape)
         off += n
-    ts = train.TrainState.__new__(train.TrainState)
-    ts.sess, ts.net, ts.params, ts.flat = sess, net, net.params, flat
-    ts._wgrad_events, ts.reg_scopes = None, []
-    ts.momentum, ts.weight_decay, ts.double_bias, ts.bias_decay = 0.9, 1e-4, False, False
-    ts.fuse_chain, ts.pipe_dgrads, ts.winograd, ts.h2_train = True, True, (4, 64, True), 1
-    ts.wgrad_stream, ts.wgrad_tn, ts.wgrad_h2, ts.prep_stream = 2, True, True, False
+    ts = train.TrainState(sess, net, momentum=0.9, weight_decay=1e-4)
+    ts.params, ts.flat = net.params, flat
+    ts.winograd, ts.h2_train = (4, 64, True), 1
+    ts.wgrad_stream, ts.wgrad_h2, ts.prep_stream = 2, True, False
     ts.solver_in_sweep, ts.SOLVER_CHUNK, ts.lr = in_sweep, chunk, 1e-4
     ts.world_size, ts.all_reduce = 2, FakeExchange(bucket)
     order, sends = [], []
@@ -496,3 +494,123 @@ def test_data_parallel_sweep_updates_behind_the_exchange_and_equals_the_update_a
     sent_at_wait = min(w[1] for w in waits)
     in_sweep_updates = order1[1][:len(order1[1]) - 1]
     assert all(offs[w] >= sent_at_wait for w in in_sweep_updates[:3])
+
+
+# ---- the handle's declaration (TrainState.__init__, TrainState.SWITCHES) ------------------------------------------------------------
+DEFAULTS = dict(fuse_chain=True, pipe_dgrads=True, prep_stream=True, solver_in_sweep=True, winograd=None, h2_train=None, wgrad_tn=True,
+                wgrad_h2=False, wgrad_stream=0, world_size=1, force_dp=False, all_reduce=None, lr=None, flop_ledger=None, pending_slots=None)
+OTHER = dict(fuse_chain=False, pipe_dgrads=False, prep_stream=False, solver_in_sweep=False, winograd=(4, 64, True), h2_train=1, wgrad_tn=False,
+             wgrad_h2=True, wgrad_stream=2, world_size=2, force_dp=True, all_reduce=FakeExchange(1))      # another value of every switch
+
+
+def handle(monkeypatch, seed=0):
+    from frcnn_hip import train
+    ops = FakeOps()
+    monkeypatch.setattr(train, "ops", ops)
+    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: FakeStream())
+    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
+    sess = FakeSession()
+    net, seeds = build(sess, seed)
+    ts = train.TrainState(sess, net)
+    ts.params.update(net.params)                             # (what build() fills)
+    return ts, net, seeds, ops
+
+
+def test_the_constructors_defaults_are_a_complete_configuration(monkeypatch):
+    """A handle straight from the constructor runs a sweep and the solver with no attribute assigned; the same launches and bits as a
+    handle that has every default assigned explicitly; and neither the sweep nor apply() creates a field __init__ does not declare."""
+    from frcnn_hip import train
+    ts0, n0, seeds0, ops0 = handle(monkeypatch)
+    for name, v in DEFAULTS.items():
+        assert vars(ts0)[name] is v or vars(ts0)[name] == v, name
+    declared = set(vars(ts0))
+    assert set(train.TrainState.SWITCHES) <= set(DEFAULTS) and set(DEFAULTS) <= declared
+    ts0._sweep(seeds0, FakeStream())
+    ts0.apply(1e-4)
+    ts0.regularization_value()
+    assert set(vars(ts0)) == declared
+    ts1, n1, seeds1, ops1 = handle(monkeypatch)
+    for name, v in DEFAULTS.items():
+        setattr(ts1, name, v)
+    ts1._sweep(seeds1, FakeStream())
+    ts1.apply(1e-4)
+    assert ops0.log == ops1.log and ops0.log["wgrad"] == 13 and ops0.log["sgd_range"] == 1
+    for sc in n0.params:
+        assert torch.equal(n0.params[sc].grad_w, n1.params[sc].grad_w) and torch.equal(n0.params[sc].w, n1.params[sc].w), sc
+        assert float(n0.params[sc].acc_w.abs().max()) > 0
+
+
+def test_switches_names_the_switch_group_of_the_constructor():
+    """TrainState.SWITCHES against the source of __init__: exactly the fields assigned under its `switches` comment, in that order."""
+    import inspect
+    import re
+    from frcnn_hip import train
+    lines = inspect.getsource(train.TrainState.__init__).splitlines()
+    marks = [i for i, ln in enumerate(lines) if ln.strip().startswith("# ----")]
+    assert len(marks) == 3 and "switches" in lines[marks[0]] and "per-run inputs" in lines[marks[1]] and "private state" in lines[marks[2]]
+    group = [n for ln in lines[marks[0] + 1:marks[1]] for n in re.findall(r"self\.(\w+)", ln.split(" = ")[0])]
+    assert tuple(group) == train.TrainState.SWITCHES and len(set(group)) == len(group) == 12
+    assert type(train.TrainState.__dict__["SOLVER_CHUNK"]) is int            # stays a class attribute
+
+
+def test_every_switch_changes_the_replay_signature(monkeypatch):
+    from frcnn_hip import train
+    assert set(OTHER) == set(train.TrainState.SWITCHES)
+    a, b = handle(monkeypatch)[0], handle(monkeypatch)[0]
+    base = a.replay_signature()
+    assert base == b.replay_signature() and len(base) == 4 + len(train.TrainState.SWITCHES)
+    hash(base)                                               # it is part of a dictionary key
+    for name in train.TrainState.SWITCHES:
+        setattr(b, name, OTHER[name])
+        sig = b.replay_signature()
+        where = [i for i, (x, y) in enumerate(zip(base, sig)) if x != y]
+        assert where == [4 + train.TrainState.SWITCHES.index(name)], name
+        setattr(b, name, DEFAULTS[name])
+        assert b.replay_signature() == base
+    # equal fields, two exchanges: equal apart from the exchange's identity
+    a.all_reduce, b.all_reduce = FakeExchange(1), FakeExchange(1)
+    i = 4 + train.TrainState.SWITCHES.index("all_reduce")
+    sa, sb = a.replay_signature(), b.replay_signature()
+    assert sa[:i] + sa[i + 1:] == sb[:i] + sb[i + 1:] and (sa[i], sb[i]) == (id(a.all_reduce), id(b.all_reduce)) and sa[i] != sb[i]
+    a.winograd = [4, 64, True]                               # a list reads as the tuple
+    b.winograd, b.all_reduce = (4, 64, True), a.all_reduce
+    assert a.replay_signature() == b.replay_signature()
+    for k, v in dict(momentum=0.5, weight_decay=1e-3, double_bias=True, bias_decay=True).items():
+        setattr(b, k, v)
+        assert b.replay_signature() != a.replay_signature(), k
+        setattr(b, k, vars(a)[k])
+
+
+def test_configure_train_op_and_the_solver_wrapper_assign_declared_fields_only(monkeypatch):
+    sys.path.insert(0, os.path.join(ROOT, "tf-faster-rcnn_amd", "lib"))
+    from model.config import cfg
+    from model.train_val import SolverWrapper
+    from nets.network import Network
+    ts, net, _, _ = handle(monkeypatch)
+    for k in ("WINOGRAD", "WINOGRAD_TRAIN", "WINOGRAD_DGRAD", "MFMA_H2", "H2_TRAIN", "WGRAD_H2", "WGRAD_TN", "PREP_STREAM"):
+        monkeypatch.setitem(cfg.HIP, k, True)
+    monkeypatch.setitem(cfg.HIP, "WGRAD_STREAM", 2)
+    declared = set(vars(ts))
+    Network.configure_train_op(ts)
+    assert set(vars(ts)) == declared
+    assert ts.winograd is not None and ts.h2_train is not None and ts.wgrad_h2 is True and ts.wgrad_tn is True and ts.wgrad_stream == 2
+    ex = FakeExchange(1)
+    sw = SolverWrapper(ts.sess, net, None, all_reduce=ex, world_size=2, force_dp=True)
+    assert set(vars(sw.state)) == declared
+    assert sw.state.all_reduce is ex and sw.state.world_size == 2 and sw.state.force_dp is True and sw.state.data_parallel()
+
+
+def test_only_the_depthwise_parameter_says_dw():
+    from frcnn_hip import train
+    assert train.Param.dw is False and train.DwParam.dw is True
+
+
+def test_exchange_caps_reads_the_exchange_once(monkeypatch):
+    from frcnn_hip import train
+    assert train.exchange_caps(None) == (False, False)
+    assert train.exchange_caps(lambda flat: flat) == (False, False)                        # the plain callable of parallel.py
+    assert train.exchange_caps(FakeExchange(1)) == (True, True)
+    one = FakeExchange(1)
+    one.multi_stream = False
+    assert train.exchange_caps(one) == (True, False)
+    assert train.exchange_caps(types.SimpleNamespace(multi_stream=True)) == (False, False)  # no ready(): not the bucketed interface

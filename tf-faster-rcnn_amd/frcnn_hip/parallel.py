@@ -113,6 +113,7 @@ class BucketedAllReduce(object):
 
     def __init__(self, group=None, bucket_bytes=64 << 20):
         self.group, self.bucket = group, max(1, int(bucket_bytes) // 4)
+        self._order = None             # _order_after's stream, made at its first use and kept across steps
         self.reset()
 
     host_s = 0.0                       # host seconds spent inside torch.distributed calls (sends + waits), cumulative: bench.py reports it
@@ -132,7 +133,7 @@ class BucketedAllReduce(object):
         streams = [st for st in (streams or []) if st is not None]
         if len(streams) <= 1:
             return streams[0] if streams else None
-        if getattr(self, "_order", None) is None:
+        if self._order is None:
             self._order = torch.cuda.Stream(device=streams[0].device)
         for st in streams:
             ops.st_wait_stream(self._order, st)

@@ -16,6 +16,7 @@ from . import ACT_NONE, ACT_RELU, ACT_RELU6, ops
 
 class Param(object):
     """One trainable filter (+ optional bias) on the device."""
+    dw = False
 
     def __init__(self, scope, wf, bias, scale_np, bias_trainable, flat_w, flat_b, master_hwio=None):
         dev = wf.device
@@ -58,6 +59,14 @@ class DwParam(object):
         self.bias = self.acc_b = self.grad_b = None
 
 
+def exchange_caps(ar):
+    """(overlapped, multi_stream) of a gradient exchange, which is a foreign object: None, a plain callable f(flat) (parallel.py), a
+    parallel.BucketedAllReduce or a test's stand-in.  overlapped: it has the bucketed interface (ready / wait_sent / finish) that the
+    reverse sweep feeds range by range; multi_stream: its ready() orders a collective after EVERY stream it is given."""
+    overlapped = ar is not None and hasattr(ar, "ready")
+    return overlapped, overlapped and bool(getattr(ar, "multi_stream", False))
+
+
 class TrainState(object):
     """Owns the parameters, their momentum buffers and ONE flat gradient buffer (so data-parallel
     training is a single RCCL all-reduce, or a few bucketed ones, over contiguous memory)."""
@@ -66,13 +75,24 @@ class TrainState(object):
         self.sess, self.net = sess, net
         self.momentum, self.weight_decay = momentum, weight_decay
         self.double_bias, self.bias_decay = double_bias, bias_decay
-        self.params = {}
-        self.flat = None
-        self.reg_scopes = []
-        self._wgrad_events = None
+        self.params, self.flat, self.reg_scopes = {}, None, []
+        # ---- switches: what decides WHICH launches a step makes (SWITCHES names exactly this group; replay_signature carries it)
         self.fuse_chain = True                                  # see _sweep (False: separate relu_bwd / copy / h2_split passes; tests)
         self.pipe_dgrads = True                                 # see _sweep (False: frcnn_conv2d_dgrad_strided for every strided / odd-width layer; tests)
         self.prep_stream = True                                 # sess.prepared: weight-only launches re-run by the solver on a side stream
+        self.solver_in_sweep = True                             # see _sweep (False: the whole update in apply(); tests)
+        self.winograd, self.h2_train = None, None               # data gradients: Winograd (m, min channels, 7x7) / frcnn_gemm_h2 from so many tiles; None = off
+        self.wgrad_tn, self.wgrad_h2, self.wgrad_stream = True, False, 0      # filter gradients: csrc/wgrad_tn.hip, its fp16 pipe, how many side streams
+        self.world_size, self.force_dp, self.all_reduce = 1, False, None      # see data_parallel; the gradient exchange (see exchange_caps)
+        # ---- per-run inputs: the step's learning rate, bench.py's ledger (count_flops), a resumed run's momentum slots (imported after build())
+        self.lr, self.flop_ledger, self.pending_slots = None, None, None
+        # ---- private state: apply()'s descriptor table, the regulariser's tables, streams and events (all made at their first use)
+        self._sgd_table, self._sgd_count, self._sgd_done_from, self._sgd_offsets, self._sgd_entry = None, 0, None, None, {}
+        self._reg_in_sweep, self._reg_buf, self._reg_tables, self._reg_keep = False, None, None, None
+        self._solver_stream, self._solver_events, self._wgrad_stream_objs, self._wgrad_events = None, [], [], None
+
+    SWITCHES = ("fuse_chain", "pipe_dgrads", "prep_stream", "solver_in_sweep", "winograd", "h2_train", "wgrad_tn", "wgrad_h2", "wgrad_stream",
+                "world_size", "force_dp", "all_reduce")
 
     def build(self):
         """Call after one TRAIN forward (which packs every filter and fills net._tape)."""
@@ -115,14 +135,13 @@ class TrainState(object):
         """True when the step runs under the data-parallel rules: more than one replica, or `force_dp` (bench.py --dp-constrained: one
         replica with everything a multi-GPU step does -- at most one filter-gradient side stream, the bucketed all-reduce issued from inside
         the sweep over a one-rank RCCL group, no captured sweep -- so that the step an 8-GPU run executes per GPU can be timed at N = 1)."""
-        return int(getattr(self, "world_size", 1)) > 1 or bool(getattr(self, "force_dp", False))
+        return int(self.world_size) > 1 or bool(self.force_dp)
 
     def count_flops(self, pipe, flops):
         """Ledger of the reverse sweep's matrix work per matrix pipe ("h2": frcnn_gemm_h2 / frcnn_conv2d_wgrad_h2, "f32": the f32-MFMA
         kernels); bench.py prices a training step per pipe with it (host arithmetic on launch shapes, nothing on the device)."""
-        led = getattr(self, "flop_ledger", None)
-        if led is not None:
-            led[pipe] = led.get(pipe, 0) + int(flops)
+        if self.flop_ledger is not None:
+            self.flop_ledger[pipe] = self.flop_ledger.get(pipe, 0) + int(flops)
 
     def backward(self, seeds, fuse_solver=False):
         """seeds: list of (tensor, grad) for network outputs.  Fills every Param.grad_*.
@@ -132,7 +151,7 @@ class TrainState(object):
         momentum of those parameters are updated when this returns, and the caller MUST complete the step with apply(self.lr, ...), which
         updates the rest.  With the default, backward() only computes gradients: calling it twice, inspecting gradients, accumulating
         them or skipping a step leaves the parameters alone."""
-        if getattr(self, "_sgd_done_from", None) is not None:
+        if self._sgd_done_from is not None:
             raise RuntimeError("TrainState.backward: the previous sweep updated part of the parameters inside the sweep (fuse_solver=True) "
                                "and apply() never completed that step")
         main = torch.cuda.current_stream()
@@ -140,33 +159,37 @@ class TrainState(object):
             return self._sweep(seeds, main, bool(fuse_solver))
 
     def replay_signature(self):
-        """Everything about this solver handle that decides WHICH launches a step makes (a recorded step is valid for one signature)."""
-        ar = getattr(self, "all_reduce", None)
-        return (float(self.momentum), float(self.weight_decay), bool(self.double_bias), bool(self.bias_decay), bool(self.fuse_chain),
-                bool(self.pipe_dgrads), bool(self.prep_stream), bool(getattr(self, "solver_in_sweep", True)), int(getattr(self, "world_size", 1)),
-                bool(getattr(self, "force_dp", False)), None if ar is None else id(ar))
+        """Everything about this solver handle that decides WHICH launches a step makes (a recorded step is valid for one signature):
+        the solver's constants and one value per name in SWITCHES (the exchange by identity)."""
+        def value(name, v):
+            if name == "all_reduce":
+                return None if v is None else id(v)
+            return tuple(v) if isinstance(v, (list, tuple)) else v
+        return ((float(self.momentum), float(self.weight_decay), bool(self.double_bias), bool(self.bias_decay))
+                + tuple(value(n, vars(self)[n]) for n in self.SWITCHES))
 
     def _sweep(self, seeds, main, fuse_solver=False):
         sess, net = self.sess, self.net
-        grads = {}
-        for t, g in seeds:
-            grads[t.data_ptr()] = g
+        grads = {t.data_ptr(): g for t, g in seeds}
         needs = net._requires_grad
         # Filter gradients on side streams (cfg.HIP.WGRAD_STREAM = how many): a wgrad only feeds the solver, while the data-gradient
         # chain is what the next record waits for -- at one image per step neither fills 256 CUs, so they run side by side.  Each side
         # stream executes its wgrads in tape order with its OWN transposed-operand scratch and split-K workspace, sees dY through an
         # event recorded after the activation gradient, and is joined before backward() returns.  Data parallel: one side stream, so
         # that "everything behind this offset of the flat gradient is final" holds on the stream the collective is issued from.
-        nside = int(getattr(self, "wgrad_stream", 0))
-        ar = getattr(self, "all_reduce", None)
-        dp = self.data_parallel() and ar is not None and hasattr(ar, "ready")        # the bucketed, overlapped exchange (parallel.BucketedAllReduce)
-        if self.data_parallel() and not (dp and getattr(ar, "multi_stream", False)):
+        nside = int(self.wgrad_stream)
+        ar = self.all_reduce
+        overlapped, multi_stream = exchange_caps(ar)
+        dp = self.data_parallel() and overlapped                 # the bucketed, overlapped exchange (parallel.BucketedAllReduce)
+        any_side = not self.data_parallel() or (dp and multi_stream)      # may filter gradients (and the in-sweep solver) use every side stream?
+        if not any_side:
             nside = min(nside, 1)                                # a plain all-reduce callable orders itself after ONE stream
-        sides = self._wgrad_side_streams(nside)
+        while len(self._wgrad_stream_objs) < nside:
+            self._wgrad_stream_objs.append(torch.cuda.Stream(device=sess.device))
+        sides = self._wgrad_stream_objs[:nside]
         turn = [0]
         if self._wgrad_events is None:
             self._wgrad_events = [torch.cuda.Event() for _ in range(16)]
-
         pins = [ops.pinned_stream(st) for st in sides]
         events = self._wgrad_events
 
@@ -178,22 +201,22 @@ class TrainState(object):
         # regulariser value reads the filters BEFORE any update: it opens the solver stream's step.
         self._sgd_done_from = None
         solver = None
-        if (fuse_solver and sides and (not self.data_parallel() or (dp and getattr(ar, "multi_stream", False)))
-                and getattr(self, "_sgd_table", None) is not None and getattr(self, "lr", None) is not None
-                and getattr(self, "solver_in_sweep", True) and not any(getattr(p, "dw", False) for p in self.params.values())):
-            solver = self._solver_stream_obj()
+        if (fuse_solver and sides and any_side and self._sgd_table is not None and self.lr is not None
+                and self.solver_in_sweep and not any(p.dw for p in self.params.values())):
+            if self._solver_stream is None:
+                self._solver_stream = torch.cuda.Stream(device=sess.device)
+            solver = self._solver_stream
             ops.st_wait_stream(solver, main)                     # (the previous step's apply() -- nothing else of this step matters to it)
             with ops.pinned_stream(solver):
                 self.regularization_loss(self._reg_total())
             self._reg_in_sweep = True
             self._sgd_done_from = self._sgd_count
         pending = [0]                                            # filter gradients enqueued since the last solver launch
-
-        gs = 1.0 / float(getattr(self, "world_size", 1)) if self.data_parallel() else 1.0     # the mean over replicas, folded into the update
+        gs = 1.0 / float(self.world_size) if self.data_parallel() else 1.0     # the mean over replicas, folded into the update
 
         def solver_step(first):
             """update table[first, done_from) on the solver stream"""
-            while len(self._solver_events) < 1 + len(sides):     # (cfg.HIP.WGRAD_STREAM is not bounded)
+            while len(self._solver_events) < 1 + len(sides):     # one per stream it waits for (cfg.HIP.WGRAD_STREAM is not bounded)
                 self._solver_events.append(torch.cuda.Event())
             for i, st in enumerate([main] + list(sides)):
                 ev = self._solver_events[i]
@@ -236,7 +259,7 @@ class TrainState(object):
         # the gradient filter) go through sess.prepared (runtime.PreparedFilters): after the first step the solver re-runs them on a
         # side stream right after its update, beside the next forward pass, and this sweep finds them done.
         prep = sess.prepared
-        prep.enabled = bool(getattr(self, "prep_stream", True)) and not getattr(self, "graph", False)      # (a captured sweep prepares inline)
+        prep.enabled = bool(self.prep_stream)
         prepared = prep.get
 
         # Elementwise passes of the chain rule folded into the launches on either side of them (cfg-free; `fuse_chain = False` keeps the
@@ -249,8 +272,8 @@ class TrainState(object):
         #    buffer instead of copying it; the convolution that later adds its own data gradient reads it as the launch's residual and
         #    writes a fresh buffer (the borrowed one is still being read by the filter gradient on a side stream);
         #  * operand planes of dY for a following frcnn_gemm_h2 data gradient come out of the Winograd output transform (`emitted`).
-        fuse = bool(getattr(self, "fuse_chain", True))
-        pipe = bool(getattr(self, "pipe_dgrads", True))         # strided 3x3 / odd-width 1x1 data gradients on the matrix pipe (False: gather kernel)
+        fuse = bool(self.fuse_chain)
+        pipe = bool(self.pipe_dgrads)         # strided 3x3 / odd-width 1x1 data gradients on the matrix pipe (False: gather kernel)
         producer = {}
         if fuse:
             for r in net._tape:
@@ -280,7 +303,7 @@ class TrainState(object):
 
         def h2_dgrad(r):
             """Does the record's data gradient run as frcnn_gemm_h2 (dX = dY W, K = Cout)?  (cfg.HIP.H2_TRAIN)"""
-            if r["k"] != 1 or r["stride"] != 1 or tuple(r["pad"]) != (0, 0, 0, 0) or getattr(self, "h2_train", None) is None:
+            if r["k"] != 1 or r["stride"] != 1 or tuple(r["pad"]) != (0, 0, 0, 0) or self.h2_train is None:
                 return False
             yy, wf = r["y"], sess.conv_info[r["scope"]]["w"]
             Mr, Co, Ci = yy.numel() // yy.shape[-1], yy.shape[-1], wf.shape[3]
@@ -380,24 +403,21 @@ class TrainState(object):
             p = self.params.get(sc)
             if p is not None:
                 def wgrad(sfx, side, gy=gy, x=x, p=p, k=k, stride=stride, pad=pad, OH=OH, OW=OW, M=M, Cout=Cout):
-                    if getattr(self, "wgrad_tn", True) and ops.conv2d_wgrad_supported(x.shape[-1], Cout) and p.K == k * k * x.shape[-1]:
+                    if self.wgrad_tn and ops.conv2d_wgrad_supported(x.shape[-1], Cout) and p.K == k * k * x.shape[-1]:
                         # dW = dY^T X straight from the two tensors as they lie (csrc/wgrad_tn.hip): no transposed copies, no im2col
-                        ops.conv2d_wgrad(gy, x, k, k, stride, pad, p.grad_w, h2=bool(getattr(self, "wgrad_h2", False)))
-                        self.count_flops("h2" if getattr(self, "wgrad_h2", False) else "f32", 2 * M * Cout * p.K)
-                        if p.bias is not None:
-                            ops.colsum(gy.view(M, Cout), p.grad_b)
-                        if dp:
-                            ar.ready(self.flat, p.grad_w.data_ptr(), side, sides)
-                        return
-                    Mp = (M + 31) // 32 * 32
-                    gyT = ops.transpose_pad(gy.view(M, Cout), Mp, out=sess.buf("bwd/gyT" + sfx, (Cout, Mp)))
-                    if k == 1 and stride == 1:
-                        xT = ops.transpose_pad(x.view(M, x.shape[-1]), Mp, out=sess.buf("bwd/xT" + sfx, (x.shape[-1], Mp)))
+                        h2 = bool(self.wgrad_h2)
+                        ops.conv2d_wgrad(gy, x, k, k, stride, pad, p.grad_w, h2=h2)
+                        self.count_flops("h2" if h2 else "f32", 2 * M * Cout * p.K)
                     else:
-                        xT = ops.im2col_t(x, k, k, stride, pad, OH, OW, Mp, out=sess.buf("bwd/xT" + sfx, (k * k * x.shape[-1], Mp)))
-                    # dW_folded[n][(kh,kw,c)] = sum_m gyT[n][m] * xT[(kh,kw,c)][m]   -- the forward MFMA kernel
-                    ops.conv2d(gyT.view(1, 1, Cout, Mp), xT.view(xT.shape[0], 1, 1, Mp), None, 1, 1, out=p.grad_w.view(1, 1, Cout, p.K))
-                    self.count_flops("f32", 2 * M * Cout * p.K)
+                        Mp = (M + 31) // 32 * 32
+                        gyT = ops.transpose_pad(gy.view(M, Cout), Mp, out=sess.buf("bwd/gyT" + sfx, (Cout, Mp)))
+                        if k == 1 and stride == 1:
+                            xT = ops.transpose_pad(x.view(M, x.shape[-1]), Mp, out=sess.buf("bwd/xT" + sfx, (x.shape[-1], Mp)))
+                        else:
+                            xT = ops.im2col_t(x, k, k, stride, pad, OH, OW, Mp, out=sess.buf("bwd/xT" + sfx, (k * k * x.shape[-1], Mp)))
+                        # dW_folded[n][(kh,kw,c)] = sum_m gyT[n][m] * xT[(kh,kw,c)][m]   -- the forward MFMA kernel
+                        ops.conv2d(gyT.view(1, 1, Cout, Mp), xT.view(xT.shape[0], 1, 1, Mp), None, 1, 1, out=p.grad_w.view(1, 1, Cout, p.K))
+                        self.count_flops("f32", 2 * M * Cout * p.K)
                     if p.bias is not None:
                         ops.colsum(gy.view(M, Cout), p.grad_b)
                     if dp:
@@ -411,7 +431,7 @@ class TrainState(object):
                 mk = relu_mask(x) if fuse else None             # x itself when it is a ReLU output: the gradient's mask
                 lent = key in borrowed                          # an identity shortcut's gradient waits there, in somebody else's buffer
                 wf = sess.conv_info[sc]["w"]
-                wino = getattr(self, "winograd", None)          # (m, min channels) set by the Network from cfg.HIP, or None
+                wino = self.winograd                            # (m, min channels) set by the Network from cfg.HIP, or None
                 Cin = wf.shape[3]
                 flipped = stride == 1 and Cout % 32 == 0
                 up_h, up_w = (OH - 1) * stride + 1, (OW - 1) * stride + 1
@@ -523,32 +543,18 @@ class TrainState(object):
 
     SOLVER_CHUNK = 32
 
-    def _solver_stream_obj(self):
-        if getattr(self, "_solver_stream", None) is None:
-            self._solver_stream = torch.cuda.Stream(device=self.sess.device)
-            self._solver_events = [torch.cuda.Event() for _ in range(8)]
-        return self._solver_stream
-
     def _reg_total(self):
-        if getattr(self, "_reg_buf", None) is None:
+        if self._reg_buf is None:
             self._reg_buf = torch.zeros((1,), dtype=torch.float32, device=self.sess.device)
         return self._reg_buf
 
     def regularization_value(self):
         """Device tensor [1]: the slim L2 term of this step's weights (network.py:315-317) -- computed by the sweep on the solver stream
         when that is active (before its first update), else here."""
-        if not getattr(self, "_reg_in_sweep", False):
+        if not self._reg_in_sweep:
             self.regularization_loss(self._reg_total())
         self._reg_in_sweep = False
         return self._reg_total()
-
-    def _wgrad_side_streams(self, n):
-        have = getattr(self, "_wgrad_stream_objs", None)
-        if have is None:
-            have = self._wgrad_stream_objs = []
-        while len(have) < n:
-            have.append(torch.cuda.Stream(device=self.sess.device))
-        return have[:n]
 
     # ---- solver --------------------------------------------------------------------------------------
     def apply(self, lr, world_size=1, all_reduce=None):
@@ -557,16 +563,17 @@ class TrainState(object):
         bucketed interface (parallel.BucketedAllReduce: backward() hands it every finished range), otherwise in one call
         here -- and the mean over replicas is folded into the SGD kernel (grad_scale = 1 / world_size)."""
         if all_reduce is not None and (world_size > 1 or self.data_parallel()):
-            if hasattr(all_reduce, "finish"):
+            if exchange_caps(all_reduce)[0]:
                 all_reduce.finish(self.flat)              # ranges not yet handed over + wait for the ones in flight
             else:
                 all_reduce(self.flat)
         gs = 1.0 / float(world_size)
         self.sess.prepared.join()                    # (a step that used none of the side stream's buffers has not waited for it yet)
-        if getattr(self, "_sgd_table", None) is None:
-            entries = []
+        if self._sgd_table is None:
+            entries, self._sgd_entry = [], {}          # scope -> index of its first descriptor (filter, then bias)
             for p in self.params.values():
-                if getattr(p, "dw", False):          # gradient already carries the BN-fold scale; no L2 term (MOBILENET.REGU_DEPTH False)
+                self._sgd_entry[p.scope] = len(entries)
+                if p.dw:          # gradient already carries the BN-fold scale; no L2 term (MOBILENET.REGU_DEPTH False)
                     entries.append((p.w, p.acc_w, None, p.grad_w, None, p.K, 1.0, 0.0))
                     continue
                 wd = self._wd(p.scope)
@@ -579,11 +586,7 @@ class TrainState(object):
             # gradient offset of every descriptor inside the flat buffer (ascending: the table is in forward order like the buffer)
             self._sgd_offsets = None if self.flat is None else [(e[3].data_ptr() - self.flat.data_ptr()) // 4 for e in entries]
             assert self._sgd_offsets is None or self._sgd_offsets == sorted(self._sgd_offsets)
-            self._sgd_entry, i = {}, 0                 # scope -> index of its first descriptor (filter, then bias)
-            for p in self.params.values():
-                self._sgd_entry[p.scope] = i
-                i += 1 if (getattr(p, "dw", False) or p.bias is None) else 2
-        left = self._sgd_count if getattr(self, "_sgd_done_from", None) is None else self._sgd_done_from      # (the sweep updated the rest)
+        left = self._sgd_count if self._sgd_done_from is None else self._sgd_done_from      # (the sweep updated the rest)
         if left != self._sgd_count and float(lr) != float(self.lr):
             raise RuntimeError("TrainState.apply(lr=%r): the reverse sweep already updated part of the parameters with TrainState.lr = %r"
                                % (lr, self.lr))
@@ -601,7 +604,7 @@ class TrainState(object):
         (Session.h2_planes & co. wait for them at their first use: PreparedFilters.wait_planes)."""
         self.sess.device_filters_moved = True        # (Session.winograd_params: later first uses derive from the live device filters)
         for p in self.params.values():
-            if getattr(p, "dw", False):
+            if p.dw:
                 ops.dwconv3x3_refold(p.w, p.scale, p.wf)
 
         def derived():
@@ -617,25 +620,22 @@ class TrainState(object):
         self.sess.prepared.invalidate()
 
     def _wd(self, scope):
-        wd = self.net.weight_decay_for(scope) if hasattr(self.net, "weight_decay_for") else None
+        wd = self.net.weight_decay_for(scope)
         return self.weight_decay if wd is None else wd
 
     # ---- checkpoint view (tf.train.Saver saves the variables AND the optimizer slots `<variable>/Momentum`) ----------
-    def _names(self, p):
-        return p.scope + "/weights", p.scope + "/biases"
-
     def export_variables(self, slots=True):
         """{TF/slim variable name: ndarray in the variable's own layout (HWIO filters, [in,out] matrices)} of every TRAINED
         parameter, read back from the device master copies (packed [Cout][KH][KW][Cin]); with slots=True also the momentum
         accumulators under `<name>/Momentum` (MomentumOptimizer's slot name)."""
         out = {}
         for p in self.params.values():
-            if getattr(p, "dw", False):
+            if p.dw:
                 name = p.scope + "/depthwise_weights"
                 for suffix, t in (("", p.w),) + ((("/Momentum", p.acc_w),) if slots else ()):
                     out[name + suffix] = t.detach().cpu().numpy().reshape(self.sess.variables[name].shape).copy()
                 continue
-            wname, bname = self._names(p)
+            wname, bname = p.scope + "/weights", p.scope + "/biases"
             ref = self.sess.variables[wname]
             for suffix, t in (("", p.w),) + ((("/Momentum", p.acc_w),) if slots else ()):
                 hwio = t.detach().cpu().numpy().transpose(1, 2, 3, 0)          # [O,KH,KW,I] -> [KH,KW,I,O]
@@ -653,11 +653,11 @@ class TrainState(object):
         """Restore the momentum accumulators written by export_variables(slots=True)."""
         get = reader_or_dict.get_tensor if hasattr(reader_or_dict, "get_tensor") else reader_or_dict.__getitem__
         for p in self.params.values():
-            if getattr(p, "dw", False):
+            if p.dw:
                 acc = np.asarray(get(p.scope + "/depthwise_weights/Momentum"), dtype=np.float32)
                 p.acc_w.copy_(torch.from_numpy(np.ascontiguousarray(acc.reshape(tuple(p.w.shape)))))
                 continue
-            wname, bname = self._names(p)
+            wname, bname = p.scope + "/weights", p.scope + "/biases"
             acc = np.asarray(get(wname + "/Momentum"), dtype=np.float32)
             kh, kw = p.w.shape[1], p.w.shape[2]
             acc = acc.reshape(kh, kw, p.w.shape[3], p.w.shape[0]).transpose(3, 0, 1, 2)
@@ -668,7 +668,7 @@ class TrainState(object):
     def regularization_loss(self, out):
         """slim l2_regularizer(WEIGHT_DECAY): wd * sum(w^2)/2 over every conv / fc weight (network.py:315-317), all tensors in
         two launches (the master tensors are static, so the pointer table is built once)."""
-        if getattr(self, "_reg_tables", None) is None:
+        if self._reg_tables is None:
             groups = {}                                              # L2 coefficient -> tensors (MobileNet: backbone vs heads)
             for sc in self.reg_scopes:
                 p = self.params.get(sc)

@@ -27,11 +27,7 @@ class Network(object):
         self._anchor_targets = {}
         self._proposal_targets = {}
         self._layers = {}
-        self._gt_image = None
         self._act_summaries = []
-        self._score_summaries = {}
-        self._train_summaries = []
-        self._event_summaries = {}
         self._variables_to_fix = {}
         self._feat_stride = [16, ]
         self._scope = "network"
@@ -46,6 +42,7 @@ class Network(object):
         self.replay_stats = dict(eager=0, recorded=0, replayed=0)      # train_step_async under cfg.HIP.TRAIN_REPLAY
         self._replay_clock, self._train_arena, self._train_scope_key = 0, None, None     # LRU clock of the recordings, replay.Arena, the step's shape scope
         self._train_state = None
+        self._plan_batch = 0                   # images per launch that TEST-mode launch-size rules see (_plan_context); 0: as built
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
         self._h2_of = {}                       # activation address -> ops.H2 operand planes of that tensor (cfg.HIP.MFMA_H2)
         self._f32_missing = set()              # addresses of activations that exist ONLY as operand planes (never read as f32)
@@ -277,7 +274,7 @@ class Network(object):
         w, b = sess.conv_params(scope, bn_eps=bn_eps)
         Cin, Cout = x.shape[-1], w.shape[0]
         rows = x.numel() // Cin
-        G = max(1, getattr(self, "_plan_batch", 0))
+        G = max(1, self._plan_batch)
         assert rows % G == 0 and (rows // G) % group_rows == 0
         M = rows // G
         out = sess.buf(self._tag + "/" + name, (rows // group_rows, Cout))
@@ -293,7 +290,7 @@ class Network(object):
     def _mean_fusable(self, rows, cout, cin, scope, group_rows=1):
         """cfg.HIP.FUSE_TAIL_MEAN applies where the tail's last convolution runs in frcnn_gemm_h2 (TEST mode, h2-eligible shape and filter)
         and the RoI rows split evenly over the images of the batch (whole groups of `group_rows` rows per image)."""
-        G = max(1, getattr(self, "_plan_batch", 0))
+        G = max(1, self._plan_batch)
         return (bool(cfg.HIP.FUSE_TAIL_MEAN) and self._mode == "TEST" and rows % G == 0 and (rows // G) % max(1, int(group_rows)) == 0
                 and self._h2_eligible(rows, cout, cin, 1, scope)
                 and bool(cfg.HIP.H2_LAZY_SPLIT or cfg.HIP.WINOGRAD))         # its input must exist as planes: emitted by the Winograd conv2, or split lazily
@@ -559,7 +556,7 @@ class Network(object):
         whether a convolution is cut along K change the bits of the result, so neither may depend on how many images share the launch:
         TEST-mode rules see per-image rows x PLAN_IMAGES whatever the batch is (the reference is strictly batch-1, lib/model/test.py:88;
         the same image must give the same tensors at batch 1, in any slot of a batch of 4, or of 8)."""
-        B = getattr(self, "_plan_batch", 0)
+        B = self._plan_batch
         return M // B * self.PLAN_IMAGES if (B > 0 and M % B == 0) else M
 
     class _plan_context(object):
@@ -589,7 +586,7 @@ class Network(object):
         self._h2_of, self._f32_missing = {}, set()      # planes are facts about THIS build's launches (buffers are reused across builds)
         net_conv = self._image_to_head(is_training)
         self._anchor_component()
-        fused = self._fuse_tail_entry and not is_training and hasattr(self, "_fused_tail_entry")
+        fused = self._fuse_tail_entry and not is_training and hasattr(self, "_fused_tail_entry")      # a method of resnetv1 only
         rois = self._region_proposal(net_conv, is_training)
         if cfg.POOLING_MODE != "crop":
             raise NotImplementedError
@@ -808,6 +805,7 @@ class Network(object):
         assert self._mode == "TRAIN"
         with self._train_scope(sess, blobs):
             self._stage_train_inputs(sess, blobs)
+            self.configure_train_op(train_op)                # before the recording's key: replay_signature() carries what this sets
             if not cfg.HIP.TRAIN_REPLAY:
                 return self._train_step_body(sess, train_op, sess.buf(self._tag + "/train/losses", (5,))).clone()
             return self._train_step_replayed(sess, train_op)
@@ -831,10 +829,9 @@ class Network(object):
         if not train_op.params:
             with ops.unscoped():                                                  # solver state is per session, not per image shape
                 train_op.build()
-                if getattr(train_op, "pending_slots", None) is not None:          # resumed run: momentum before the first update
+                if train_op.pending_slots is not None:          # resumed run: momentum before the first update
                     train_op.import_slots(train_op.pending_slots)
                     train_op.pending_slots = None
-        self.configure_train_op(train_op)
         train_op.backward(self._loss_seeds, fuse_solver=True)
         reg = train_op.regularization_value()
         parts = [losses[k].view(1) for k in ("rpn_cross_entropy", "rpn_loss_box", "cross_entropy", "loss_box")]
@@ -842,7 +839,7 @@ class Network(object):
         def assemble():
             torch.cat(parts + [reg + parts[0] + parts[1] + parts[2] + parts[3]], out=out)
         ops.host_op(assemble)
-        train_op.apply(train_op.lr, getattr(train_op, "world_size", 1), getattr(train_op, "all_reduce", None))
+        train_op.apply(train_op.lr, train_op.world_size, train_op.all_reduce)
         self._sample_seed += 2
         return out
 
@@ -913,7 +910,7 @@ class Network(object):
             arena = self._train_arena = replay.Arena(sess, self._tag + "/train")
         arena.reset()
         prep = sess.prepared
-        steady = (ent["seen"] >= 1 and bool(train_op.params) and getattr(train_op, "_sgd_table", None) is not None
+        steady = (ent["seen"] >= 1 and bool(train_op.params) and train_op._sgd_table is not None
                   and frcnn_hip.recorder is None
                   and (not cfg.HIP.PREP_STREAM or (prep.ready_version == prep.version and len(prep.plan) > 0 and len(prep.ready) == len(prep.plan))))
         gen_before = sess.derived_generation()

@@ -24,6 +24,7 @@ dev = torch.device("cuda:0")
 shapes = {  # name: (G, M, N, K, residual, f32 out, planes out, mean rows)
     "b4c3x8":  (1, 117600, 2048, 512, True, True, True, 0),        # block4 units 1-2 conv3: residual + f32 trunk + next conv1's planes
     "b4c3x8m": (8, 14700, 2048, 512, True, False, False, 49),      # block4 unit 3 conv3 + reduce_mean (one batch entry per image)
+    "b4c3x8pm": (8, 14700, 2048, 512, "planes", False, False, 49),  # ... as shipped: the residual arrives as unit 2's operand planes
     "b3c3x8":  (1, 19152, 1024, 256, True, True, True, 0),         # block3 conv3 (23 per step)
     "b2c3x8":  (1, 75000, 512, 128, True, True, True, 0),          # block2 conv3
     "b4c3x8p": (1, 117600, 2048, 512, "planes", False, True, 0),   # ... as shipped since round 5 (cfg.HIP.H2_TRUNK_PLANES): residual read as planes, planes only out

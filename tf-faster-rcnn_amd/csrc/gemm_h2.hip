@@ -141,6 +141,9 @@ struct H2Lds {
                                                                    // PP: [wave][parity] 256 B: each wave's own 64 row scales
   static constexpr int CB_OFF = S2_OFF + (PP ? NW * 512 : (TUNE & H2_SCALES_ONCE) ? 2048 : 0);   // H2_LIGHT_BOUNDARY: [tile parity][filter scales BN | bias BN] floats
   static constexpr int TOTAL = CB_OFF + ((TUNE & H2_LIGHT_BOUNDARY) ? 2 * 2 * BN * 4 : 0);
+  // H2_LIGHT_BOUNDARY: the block scales of the BM rows of a residual given as operand planes, [tile parity] = inside STAGE 0 / 1: the
+  // second half of the stage's 1 KB scale region (the x block scales take BM * 4 <= 512 B of it, none with H2_SCALES_ONCE)
+  static constexpr int RI_OFF = S_OFF + 512;
 };
 
 template <int BM, int BN, int WM, int WN, int NS, int WPE = 2, int TUNE = 0>
@@ -158,8 +161,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   constexpr bool W21 = (TUNE & H2_STORE16) != 0;
   constexpr bool DE = (TUNE & H2_DEFERRED) != 0;
   using L = H2Lds<BM, BN, WM, WN, NS, TUNE>;
-  constexpr int XP = L::XP, WP = L::WP, S_OFF = L::S_OFF, STAGE = L::STAGE, RED_OFF = L::RED_OFF, S2_OFF = L::S2_OFF, CB_OFF = L::CB_OFF;
-  static_assert(!LTB || (!PP && NS == 2 && NW >= 3 && BN % 64 == 0), "light boundary: the two-slot one-barrier-per-slab schedule");
+  constexpr int XP = L::XP, WP = L::WP, S_OFF = L::S_OFF, STAGE = L::STAGE, RED_OFF = L::RED_OFF, S2_OFF = L::S2_OFF, CB_OFF = L::CB_OFF, RI_OFF = L::RI_OFF;
+  static_assert(!LTB || (!PP && NS == 2 && NW >= 4 && BN % 64 == 0 && BM <= 128), "light boundary: the two-slot one-barrier-per-slab schedule");
   static_assert(!DE || (LTB && W21 && BN == H2_KB), "deferred epilogue: built on the light boundary's LDS constants and counted waits");
   static_assert(!PP || (NW == 8 && NS == 3 && ONCE && BM == 256 && WM == 64 && BN == 128 && WN == 64),
                 "ping-pong geometry: 8 waves as 4 (M) x 2 (N), waves 0-3 = the upper half of the rows");
@@ -188,7 +191,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   unsigned a_off[LA], b_off[LB], s_off[SL];
   const char* i_xb = nullptr; const char* i_wb = nullptr; const char* i_sb = nullptr;  // wave-uniform bases, advanced per slab
   int i_tile = tile0, i_step = 0, i_par = 0, c_par = 0;       // *_par: parity of the running 128-k block count (issue / compute side)
-  int i_g = 0, i_bn0 = 0, i_cpar = 0, c_cpar = 0;             // LTB: batch entry / first column of the tile being issued; tile parities
+  int i_g = 0, i_bm0 = 0, i_bn0 = 0, i_cpar = 0, c_cpar = 0;  // LTB: batch entry / first row / first column of the tile being issued; tile parities
   int pend = 0;                                               // LTB: vector-memory instructions this wave issued AFTER its last slab load
 #pragma unroll
   for (int t = 0; t < LB; ++t) {
@@ -207,7 +210,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     tile_coords(tl, g, mt, nt);
     const int bm0 = mt * BM, bn0 = nt * BN;
     const size_t row0 = (size_t)g * p.M + bm0;
-    i_g = g; i_bn0 = bn0;
+    i_g = g; i_bm0 = bm0; i_bn0 = bn0;
     i_xb = (const char*)p.x + row0 * p.K * 2;
     i_wb = (const char*)p.w + ((size_t)(p.wshare ? 0 : g) * 2 * p.N + bn0) * p.K * 2;
     i_sb = (const char*)(p.x_inv + row0);
@@ -263,7 +266,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   };
 
   // LTB: the column-block constants of the tile whose FIRST slab has just been issued -- the filter scales and the bias of its BN columns --
-  // travel to LDS with that slab (waves 1 and 2, BN / 64 four-byte direct-to-LDS loads each), into the parity region of the tile.  The
+  // travel to LDS with that slab (waves 1 and 2, BN / 64 four-byte direct-to-LDS loads each; wave 3: the row block scales of a residual
+  // given as operand planes, BM / 64 loads), into the parity region of the tile.  The
   // tile start and the epilogue then read them with ds_read: no global load whose wait would drain the stores / slabs in flight.
   auto issue_cb = [&]() {
     const unsigned cb = lds0 + CB_OFF + i_cpar * (2 * BN * 4);
@@ -277,6 +281,14 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
 #pragma unroll
       for (int j = 0; j < BN / 64; ++j)
         h2_glds4((unsigned)(lane * 4), uniform_ptr((const char*)(p.bias + i_bn0 + j * 64)), __builtin_amdgcn_readfirstlane(cb + BN * 4 + j * 256));
+    }
+    // a residual given as operand planes: the block scales of the tile's rows for its column block (one float per lane and 64 rows; rows
+    // past the entry re-read its last row), read by the first fold when it converts the raw plane words
+    if (wave == 3 && p.resp) {
+      const char* rb = (const char*)(p.resp_inv + (size_t)(i_bn0 / H2_KB) * p.Mtot + (size_t)i_g * p.M + i_bm0);
+#pragma unroll
+      for (int j = 0; j < SL; ++j)
+        h2_glds4((unsigned)(min(j * 64 + lane, p.M - 1 - i_bm0) * 4), uniform_ptr(rb), __builtin_amdgcn_readfirstlane(lds0 + i_cpar * STAGE + RI_OFF + j * 256));
     }
     i_cpar ^= 1;
   };
@@ -430,9 +442,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     return __builtin_amdgcn_readfirstlane((T.bm0 + wm0 + i * 32) * p.N + T.bn0 + wn0 + j * 32);
   };
 
-  float rri[TM];                                                // DE: the residual planes' block scales of the tile's rows (raw residual: first fold)
-  (void)rri;
-  // The tile's residual (tile under the c_* cursor), sub-tile row i, RAW into tot[i][*]: always four 16-byte loads per sub-tile through ONE instruction stream --
+  // The tile's residual (tile under the c_* cursor), sub-tile row i, RAW into tot[i][*] (light boundary: from init_tot; deferred epilogue:
+  // from the drain pieces): always four 16-byte loads per sub-tile through ONE instruction stream --
   // float32 residual: quad q <- columns 8 q + 4 khalf .. + 3; residual as operand planes: the inverse of the W21 store pairing -- load 2 p
   // <- H words of columns 16 p + 8 khalf .. + 7, load 2 p + 1 <- the L words of the same columns (un-paired by v_permlane32_swap in the first
   // fold); no residual: the same loads through a zero-length descriptor return 0.  The three cases differ in descriptors and offsets
@@ -459,13 +470,32 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
       }
       pend += 4;
     }
-    if (p.resp) rri[i] = p.resp_inv[(size_t)(c_bn0 / H2_KB) * p.Mtot + (size_t)c_g * p.M + min(c_bm0 + wm0 + i * 32 + frow, p.M - 1)];
   };
   // The accumulators of a tile START at (bias + res) * 2^e_w: the filter row's scale w_inv = 2^-e_w is an exact power of two, so the
   // final  tot * w_inv  = products + bias + res  is one f32 sum evaluated in the scaled domain -- and the residual is fetched when the
   // tile starts (its latency hides under the first 128-k block; it is first touched by that block's fold) instead of after the last MFMA.
   auto init_tot = [&]() {
     if constexpr (DE) return;          // deferred epilogue: the residual arrives with the drain pieces (load_res_raw), sub-tile row by row
+    if constexpr (LTB) {
+      // Light boundary: the residual stays RAW in `tot` -- float32 words, or the plane words of a residual given as operand planes (four
+      // 16-byte loads per sub-tile either way; the planes' block scales went to LDS with the tile's first slab, issue_cb: no register
+      // holds them through the K loop) -- its loads in flight behind the previous tile's stores until the first fold of the tile, four
+      // slabs from here, un-pairs and converts the plane words and forms the scaled start value with the filter scales
+      // and the bias read from LDS: no wait on a load here.  (One instruction stream for both residual forms, load_res_raw: a branch
+      // per form made the register allocator spill.)
+      if (p.res || p.resp) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) load_res_raw(i);
+      } else {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+      }
+      return;
+    }
     // Every load of the tile start is issued before the first one is used: the filter scales and the bias of the tile's columns
     // (TN x 4 float4 each) and the residual straight into `tot`.  (Round 3 interleaved load, wait and arithmetic per 4 columns inside
     // runtime `if (p.res)` branches: ~30 dependent memory round trips per tile, as long as the whole K loop of a K = 256 tile.)
@@ -524,9 +554,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
 #pragma unroll
           for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
     }
-    // LTB: that is all -- the residual stays RAW in `tot` (its loads in flight behind the previous tile's stores) until the first fold of the
-    // tile, four slabs from here, turns it into the scaled start value with the filter scales and the bias read from LDS (fold_first).
-    if constexpr (LTB) return;
     // the filter scales and the bias of the tile's columns (issued behind the residual's loads: all of them are in flight together)
     float4 wi[TN][4], bv[TN][4];
 #pragma unroll
@@ -609,43 +636,37 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
   };
   // frcnn_gemm_h2_mean: reduce_mean over row groups instead of a result tensor (the tail's last convolution feeds only the spatial
   // mean, lib/nets/resnet_v1.py:115-125).  A 32-row accumulator block (lanes = rows) meets at most two groups (mean_rows >= 32):
-  // the rows of the group its first row belongs to, and of the next one, are added over the 32 lanes by a fixed xor butterfly
+  // the rows of the group its first row belongs to, and of the next one, are added over the 32 lanes by a fixed butterfly (h2_sum32:
+  // on the VALU, the bits of the xor butterfly over offsets 1 .. 16 = a pairwise tree in row order, tests/test_h2_mean_tree_cpu.py)
   // and written as two partial rows; k_h2_mean_finish adds a group's 2-3 blocks in ascending order.  Which rows meet in which
   // block depends only on the row index inside the batch entry, so with one batch entry per image the same RoI gives the same
-  // bits in every batch slot and at every batch size.
-  auto ep_mean = [&](const TileRef& T) {
+  // bits in every batch slot and at every batch size.  A block whose last row still lies in its first row's group meets no second
+  // group: its second partial row is neither formed nor written (k_h2_mean_finish reads slot 1 only of a block in which a group
+  // starts).  Sub-tile row i of tile T.
+  auto ep_mean = [&](const TileRef& T, int i) {
+    const int mb = T.bm0 + wm0 + i * 32;
+    if (mb >= p.M) return;                                                // wave-uniform: the block lies past the entry's rows
     const int nblk = (p.M + 31) >> 5;
+    const int m = mb + frow, g0 = mb / p.mean_rows, gid = m / p.mean_rows;
+    const bool in_a = m < p.M && gid == g0, in_b = m < p.M && gid == g0 + 1;
+    const bool two = mb - g0 * p.mean_rows + 31 >= p.mean_rows;           // wave-uniform: a second group may start inside the block
+    float* dst = p.mean_part + ((size_t)T.g * nblk + (mb >> 5)) * 2 * p.N;
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int mb = T.bm0 + wm0 + i * 32;
-      if (mb >= p.M) continue;                                            // wave-uniform: the block lies past the entry's rows
-      const int m = mb + frow, g0 = mb / p.mean_rows, gid = m / p.mean_rows;
-      const bool in_a = m < p.M && gid == g0, in_b = m < p.M && gid == g0 + 1;
-      float* dst = p.mean_part + ((size_t)T.g * nblk + (mb >> 5)) * 2 * p.N;
+    for (int j = 0; j < TN; ++j) {
+      const int n0 = T.bn0 + wn0 + j * 32 + 4 * khalf;
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n0 = T.bn0 + wn0 + j * 32 + 4 * khalf;
+      for (int q = 0; q < 4; ++q) {
+        float a[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float a[4], b[4];
+        for (int e = 0; e < 4; ++e) a[e] = h2_sum32(in_a ? tot[i][j][4 * q + e] : 0.f);
+        if (frow == 0) *(float4*)(dst + n0 + 8 * q) = make_float4(a[0], a[1], a[2], a[3]);
+        ++pend;                                                           // (vector-memory instructions actually issued: one per partial row)
+        if (two) {
+          float b[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float v = tot[i][j][4 * q + e];
-            a[e] = in_a ? v : 0.f;
-            b[e] = in_b ? v : 0.f;
-          }
-#pragma unroll
-          for (int o = 1; o < 32; o <<= 1)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              a[e] += __shfl_xor(a[e], o, 64);
-              b[e] += __shfl_xor(b[e], o, 64);
-            }
-          if (frow == 0) {
-            *(float4*)(dst + n0 + 8 * q) = make_float4(a[0], a[1], a[2], a[3]);
-            *(float4*)(dst + p.N + n0 + 8 * q) = make_float4(b[0], b[1], b[2], b[3]);
-          }
-          pend += 2;
+          for (int e = 0; e < 4; ++e) b[e] = h2_sum32(in_b ? tot[i][j][4 * q + e] : 0.f);
+          if (frow == 0) *(float4*)(dst + p.N + n0 + 8 * q) = make_float4(b[0], b[1], b[2], b[3]);
+          ++pend;
         }
       }
     }
@@ -751,7 +772,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     ep_scale_act(T);
     ep_mask(T);
     if (p.mean_part) {
-      ep_mean(T);
+#pragma unroll
+      for (int i = 0; i < TM; ++i) ep_mean(T, i);
       c_cpar ^= 1;
       return;
     }
@@ -866,14 +888,16 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         // The tile's first fold: `tot` holds the raw residual (or zeros); the start value (bias + res) * 2^e_w is formed here, from the
         // filter scales and the bias in LDS -- the same add, multiply and fma as init_tot's, bit for bit.
         const float* cbp = (const float*)(smem + CB_OFF + c_cpar * (2 * BN * 4));
-        if (DE && !p.res && p.resp) {
-          // the residual arrived as RAW plane words in the accumulator's own registers (load_res_raw): words 8 p .. 8 p + 3 = the H
+        if (!p.res && p.resp) {
+          // the residual arrived as RAW plane words in the accumulator's own registers (load_res_raw, from init_tot or, deferred
+          // epilogue, from the drain pieces): words 8 p .. 8 p + 3 = the H
           // words of columns 16 p + 8 khalf .. + 7, words 8 p + 4 .. + 7 the L words.  v_permlane32_swap of (first pair, second pair)
           // hands every lane its own two quads 2 p, 2 p + 1 (the inverse of the W21 store pairing); (h + l) is exact in f32, times the
           // block's power-of-two scale -- init_tot's expression, bit for bit.
           typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
+          for (int i = 0; i < TM; ++i) {
+            const float rri = *(const float*)(smem + c_cpar * STAGE + RI_OFF + (wm0 + i * 32 + frow) * 4);         // the row's block scale (issue_cb)
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -887,10 +911,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
                 const h4 la = __builtin_bit_cast(h4, u32x2{l0[0], l1[0]}), lb = __builtin_bit_cast(h4, u32x2{l0[1], l1[1]});
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                  tot[i][j][8 * pq + e] = ((float)ha[e] + (float)la[e]) * rri[i];
-                  tot[i][j][8 * pq + 4 + e] = ((float)hb[e] + (float)lb[e]) * rri[i];
+                  tot[i][j][8 * pq + e] = ((float)ha[e] + (float)la[e]) * rri;
+                  tot[i][j][8 * pq + 4 + e] = ((float)hb[e] + (float)lb[e]) * rri;
                 }
               }
+          }
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
@@ -1308,7 +1333,9 @@ static int run_h2(GemmH2Params& p, int cfg, hipStream_t st) {
     // cfg == -2: round 4's choice (A/B runs).  Round 5: the same tiles with the light tile boundary and 16-byte plane stores (31, 33):
     // bit-identical, 5-16 % faster on the short-K launches, indifferent elsewhere (profiles/r05_b_h2_conv3_light_boundary.txt)
     // Round 6: the deferred epilogue (cfgs 40 / 41: tile t drains under tile t + 1's first slabs) wherever a result tensor is written --
-    // not the fused-mean form (its epilogue is a reduction, kept standalone).  cfg == -7: round 5's choice (A/B runs).
+    // not the fused-mean form: its epilogue is a VALU reduction with 8-16 small stores per sub-tile row; run as drain pieces it measured
+    // no faster than standalone behind the raw planes residual (profiles/h2_mean_valu.txt: 1 021-1 025 vs 1 013-1 019 us) and took the
+    // deferred kernel to 256 VGPRs with 6 spilled.  cfg == -7: round 5's choice (A/B runs).
     // Measured (profiles/r06_d_h2_de.txt, isolated 8-image launches): it pays where the boundary is longest -- residual read as planes,
     // planes only out, the identity units of a trunk kept as planes: block3 conv3 65.6 -> 60.0 us, block4 conv3 1 190 -> 1 172 us -- and
     // costs 1-5 % where the standalone epilogue was short (float32 out without residual: its stores then sit in the next tile's slabs

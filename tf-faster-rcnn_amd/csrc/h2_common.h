@@ -56,6 +56,23 @@ __device__ __forceinline__ unsigned h2_max64(unsigned v) {
   return max(r[0], r[1]);
 }
 
+// The float32 sum over each half of the wave (lanes 0-31 / 32-63), in every lane, on the VALU: four v_add_f32_dpp inside a DPP row
+// and one v_permlane16_swap between the rows.  After step k every lane of an aligned 2^k group holds the same value, so the mirror
+// partner holds the bits of the xor partner: the result is that of the butterfly v += shfl_xor(v, 1 / 2 / 4 / 8 / 16) bit for bit,
+// i.e. a pairwise tree in lane order -- without its five ds_bpermute round trips through the LDS pipe.  All 64 lanes must call.
+template <int CTRL>
+__device__ __forceinline__ float h2_dpp_f32(float v) {
+  return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float h2_sum32(float v) {
+  v += h2_dpp_f32<0xB1>(v);
+  v += h2_dpp_f32<0x4E>(v);
+  v += h2_dpp_f32<0x141>(v);
+  v += h2_dpp_f32<0x140>(v);
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 

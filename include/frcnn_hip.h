@@ -282,6 +282,31 @@ int frcnn_prep_train_image(const void* src_d, int src_is_float, int h, int w, in
                            float* out_d, int OH, int OW, int out_c, const unsigned short* boxes_d, const int* classes_d, int G,
                            float* gt_d, void* stream);
 
+/* Baseline JPEG decode, hybrid (csrc/jpeg_host.h + csrc/jpeg_decode.hip): what PIL.Image.open(f).convert("RGB")[:, :, ::-1] computes in
+ * lib/model/test.py imdb_images / lib/roi_data_layer/minibatch.py read_image, bit for bit (libjpeg's integer rules: jpeg_idct_islow, fancy
+ * upsampling, the 16-bit YCbCr tables).  The Huffman stage runs on the HOST (no GPU involved, thread-safe, no allocation) into one
+ * contiguous coefficient buffer: uint16 quant[3][64] in natural order, then the int16 coefficients, un-dequantised, component after
+ * component, each [blocks_y][blocks_x][64] natural order, padded to whole MCUs.  Two launches turn its device copy into BGR uint8 [h][w][3],
+ * the input of frcnn_prep_image.  Geometry travels as scalars (width, height, ncomp, hs, vs = luma sampling factors).
+ * Supported: SOF0 / 8-bit SOF1, one interleaved scan, 1 component, or 3 components with ids 1, 2, 3, no Adobe APP14 segment, chroma 1x1
+ * and luma 1x1 / 2x1 / 2x2.  FRCNN_E_UNSUPPORTED: any other JPEG (progressive, arithmetic, lossless, 12-bit, 16-bit tables, CMYK, other
+ * sampling, several scans, DNL) and data that does not start with FF D8.  FRCNN_E_ARG: a damaged stream (truncated scan, bad code, DC
+ * category > 11 / AC > 10, run past coefficient 63, wrong restart marker, missing table) or a coef buffer that is too small; nothing is read past
+ * data + n or written outside the buffer whatever the bytes are.
+ *   frcnn_jpeg_info:           HOST. out8 = {width, height, ncomp, hs, vs, restart_interval, sof (0 / 1), 0}
+ *   frcnn_jpeg_coef_bytes:     384 + 128 * (blocks of all components); 0 for a geometry outside the list above
+ *   frcnn_jpeg_entropy_decode: HOST. data -> coef_h (coef_bytes >= frcnn_jpeg_coef_bytes)
+ *   frcnn_jpeg_pixels_host:    HOST statement of frcnn_jpeg_pixels (the same arithmetic header): coef_h -> bgr_h [h][w][3]
+ *   frcnn_jpeg_pixels:         coef_d (16-byte aligned) -> bgr_d; ws (16-byte aligned) of frcnn_jpeg_workspace_bytes bytes holds the sample
+ *                              planes; ws_bytes too small: FRCNN_E_ARG, nothing launched */
+int frcnn_jpeg_info(const unsigned char* data, size_t n, int* out8);
+size_t frcnn_jpeg_coef_bytes(int width, int height, int ncomp, int hs, int vs);
+int frcnn_jpeg_entropy_decode(const unsigned char* data, size_t n, void* coef_h, size_t coef_bytes);
+int frcnn_jpeg_pixels_host(const void* coef_h, int width, int height, int ncomp, int hs, int vs, unsigned char* bgr_h);
+size_t frcnn_jpeg_workspace_bytes(int width, int height, int ncomp, int hs, int vs);
+int frcnn_jpeg_pixels(const void* coef_d, int width, int height, int ncomp, int hs, int vs, unsigned char* bgr_d, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* G independent NT GEMMs in one launch (f32 MFMA): y[g][m][n] = sum_k x[g][m][k] * w[g][n][k];  K % 32 == 0. */
 int frcnn_gemm_batched_nt(const float* x_d, const float* w_d, float* y_d, int G, int M, int N, int K, void* stream);
 /* f32 "NT" GEMM on the bf16 matrix pipe with exactly split operands (csrc/gemm_x3.hip; cfg.HIP.MFMA_X3, default on in TEST mode; finite operands below the bf16 maximum -- an inf operand yields NaN, not inf): every f32 value

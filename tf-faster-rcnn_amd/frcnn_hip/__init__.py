@@ -75,6 +75,12 @@ SIGNATURES = {
     "frcnn_prep_image_shape": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P]),
     "frcnn_prep_image": (c_int, [_P, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P]),
     "frcnn_prep_train_image": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "frcnn_jpeg_info": (c_int, [_P, c_size_t, _P]),
+    "frcnn_jpeg_coef_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "frcnn_jpeg_entropy_decode": (c_int, [_P, c_size_t, _P, c_size_t]),
+    "frcnn_jpeg_pixels_host": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "frcnn_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "frcnn_jpeg_pixels": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "frcnn_gemm_batched_nt": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_winograd_filter_transform": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "frcnn_winograd_filter_transform_device": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),

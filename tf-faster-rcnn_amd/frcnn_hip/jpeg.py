@@ -1,0 +1,165 @@
+"""frcnn_hip.jpeg -- image files to BGR uint8 [h,w,3] device tensors, the input of frcnn_prep_image / frcnn_prep_train_image.
+
+A baseline JPEG takes the hybrid path: the Huffman stage on the host (frcnn_jpeg_entropy_decode, C, the GIL released), IDCT, chroma
+upsampling and colour conversion in two kernels (frcnn_jpeg_pixels).  The pixels equal `PIL.Image.open(f).convert("RGB")[:, :, ::-1]` bit
+for bit.  Every other file -- a JPEG outside the decoder's list (progressive, CMYK, ...), a damaged one, a PNG -- goes the way it always
+went: PIL on the host, then the copy; the user sees PIL's pixels or PIL's error.
+
+decode_bgr: one file, synchronous.  JpegCache / JpegPrefetcher: worker threads read files and entropy-decode into a pool of pinned
+buffers ahead of the consumer, which issues the copy and the two launches on ITS current stream; a pinned buffer is written again only
+after an event recorded behind its copy has completed."""
+import io
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_WORKERS = 8
+
+
+def _read(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src)
+    with open(src, "rb") as f:
+        return f.read()
+
+
+def pil_bgr(src):
+    """The path every image took before: BGR uint8 [h,w,3] numpy, decoded by PIL (path or bytes)."""
+    from PIL import Image
+    f = io.BytesIO(bytes(src)) if isinstance(src, (bytes, bytearray, memoryview)) else src
+    return np.ascontiguousarray(np.asarray(Image.open(f).convert("RGB"))[:, :, ::-1])
+
+
+def _is_cuda(device):
+    return torch.device(device).type == "cuda"
+
+
+def decode_bgr(src, device):
+    """File path or bytes -> BGR uint8 [h,w,3] tensor on `device`.  device 'cpu': the host statement of the kernels."""
+    data = _read(src)
+    try:
+        geom = ops.jpeg_info(data)
+        coef = ops.jpeg_entropy_decode(data, geom=geom)
+    except ops.JpegError:
+        return torch.from_numpy(pil_bgr(src)).to(device)
+    if not _is_cuda(device):
+        return torch.from_numpy(ops.jpeg_pixels_host(coef, geom))
+    return ops.jpeg_pixels(coef.to(device), geom)
+
+
+class _Slot(object):
+    __slots__ = ("buf", "ev")
+
+    def __init__(self):
+        self.buf, self.ev = None, None
+
+
+class JpegCache(object):
+    """prefetch(key, src) starts reading + entropy-decoding `src` on a worker thread if one of the `depth` pinned buffers is free;
+    get(key, src) returns the device tensor (decoding synchronously what was never prefetched)."""
+
+    MIN_SLOT_BYTES = 1 << 20         # a 480 x 640 4:2:0 image needs 0.46 MB: most slots are allocated once
+
+    def __init__(self, device, workers=4, depth=8):
+        self.device = torch.device(device)
+        self._cuda = _is_cuda(device)
+        self._pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)))
+        self._slots = [_Slot() for _ in range(max(1, int(depth)))]
+        self._free = list(range(len(self._slots)))
+        self._pending = {}           # key -> (future, slot index)
+
+    def _work(self, src, k):
+        data = _read(src)
+        try:
+            geom = ops.jpeg_info(data)
+        except ops.JpegError:
+            return ("pil", pil_bgr(src))
+        slot = self._slots[k]
+        if slot.ev is not None:
+            slot.ev.synchronize()                                # the copy that last read this buffer has finished
+        n = ops.jpeg_coef_bytes(geom)
+        if slot.buf is None or slot.buf.numel() < n:
+            slot.buf = torch.empty(max(n, self.MIN_SLOT_BYTES), dtype=torch.uint8, pin_memory=self._cuda)
+        try:
+            coef = ops.jpeg_entropy_decode(data, out=slot.buf, geom=geom)
+        except ops.JpegError:
+            return ("pil", pil_bgr(src))
+        return ("coef", geom, coef)
+
+    def prefetch(self, key, src):
+        if key in self._pending:
+            return True
+        if not self._free:
+            return False
+        k = self._free.pop()
+        self._pending[key] = (self._pool.submit(self._work, src, k), k)
+        return True
+
+    def get(self, key, src):
+        if key not in self._pending:
+            return decode_bgr(src, self.device)
+        fut, k = self._pending.pop(key)
+        try:
+            res = fut.result()
+            if res[0] == "pil":
+                return torch.from_numpy(res[1]).to(self.device, non_blocking=True)
+            _, geom, coef = res
+            if not self._cuda:
+                return torch.from_numpy(ops.jpeg_pixels_host(coef, geom))
+            coef_d = coef.to(self.device, non_blocking=True)
+            slot = self._slots[k]
+            if slot.ev is None:
+                slot.ev = torch.cuda.Event()
+            slot.ev.record(torch.cuda.current_stream())
+            return ops.jpeg_pixels(coef_d, geom)
+        finally:
+            self._free.append(k)
+
+    def close(self):
+        for fut, _ in self._pending.values():
+            fut.cancel()
+        self._pool.shutdown(wait=True)
+        self._pending = {}
+
+
+class JpegPrefetcher(object):
+    """Ordered iterator over `paths` (file paths or bytes objects) -> BGR uint8 [h,w,3] tensors on `device`; up to `depth` files are read and
+    entropy-decoded ahead by `workers` threads (a plain argument, capped at 8)."""
+
+    def __init__(self, paths, device, workers=4, depth=8):
+        self._paths = list(paths)
+        self._cache = JpegCache(device, workers=workers, depth=depth)
+        self._depth = max(1, int(depth))
+        self._i = 0
+        self._ahead = 0
+        self._fill()
+
+    def _fill(self):
+        self._ahead = max(self._ahead, self._i)
+        while self._ahead < min(len(self._paths), self._i + self._depth) and self._cache.prefetch(self._ahead, self._paths[self._ahead]):
+            self._ahead += 1
+
+    def __len__(self):
+        return len(self._paths)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._i >= len(self._paths):
+            self._cache.close()
+            raise StopIteration
+        i = self._i
+        self._i += 1
+        try:
+            return self._cache.get(i, self._paths[i])
+        finally:
+            self._fill()
+
+    next = __next__
+
+    def close(self):
+        self._cache.close()

@@ -547,6 +547,80 @@ def prep_train_image(im_d, flipped, pixel_means, im_scale, out_hw, out=None, out
     return out
 
 
+# ---- baseline JPEG decode: host Huffman stage, device IDCT + colour (csrc/jpeg_host.h, csrc/jpeg_decode.hip) ---------------------------
+JPEG_OK, JPEG_E_ARG, JPEG_E_UNSUPPORTED = 0, -1, -3
+
+
+class JpegError(_binding.FrcnnHipError):
+    """rc = JPEG_E_UNSUPPORTED (a stream outside the decoder's list, or no JPEG at all) or JPEG_E_ARG (a damaged stream)."""
+
+    def __init__(self, what, rc):
+        _binding.FrcnnHipError.__init__(self, "%s: %s" % (what, {JPEG_E_ARG: "damaged stream or bad argument",
+                                                                 JPEG_E_UNSUPPORTED: "not a supported baseline JPEG"}.get(rc, "error %d" % rc)))
+        self.rc = rc
+
+
+def _jpeg_bytes(data):
+    """bytes-like -> (object that keeps the memory alive, address, length) without a copy for bytes / numpy uint8"""
+    if isinstance(data, np.ndarray):
+        a = np.ascontiguousarray(data, dtype=np.uint8)
+        return a, a.ctypes.data, a.size
+    data = bytes(data) if not isinstance(data, bytes) else data
+    return data, ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value, len(data)
+
+
+def jpeg_info(data):
+    """HOST: geometry (width, height, ncomp, hs, vs, restart_interval, sof, 0) of a supported stream; JpegError otherwise."""
+    keep, addr, n = _jpeg_bytes(data)
+    out = (ctypes.c_int * 8)()
+    rc = lib().frcnn_jpeg_info(addr, n, out)
+    if rc != 0:
+        raise JpegError("frcnn_jpeg_info", rc)
+    return tuple(out)
+
+
+def jpeg_coef_bytes(geom):
+    return int(lib().frcnn_jpeg_coef_bytes(*[int(v) for v in geom[:5]]))
+
+
+def jpeg_entropy_decode(data, out=None, geom=None):
+    """HOST: the Huffman stage -> the coefficient buffer as a host uint8 tensor (its first jpeg_coef_bytes(geom) bytes when `out`, e.g. a
+    pinned ring slot, is larger).  ctypes releases the GIL for the call, so several threads decode side by side."""
+    keep, addr, n = _jpeg_bytes(data)
+    geom = jpeg_info(data) if geom is None else geom
+    nbytes = jpeg_coef_bytes(geom)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and not out.is_cuda
+    rc = lib().frcnn_jpeg_entropy_decode(addr, n, out.data_ptr(), out.numel())
+    if rc != 0:
+        raise JpegError("frcnn_jpeg_entropy_decode", rc)
+    return out[:nbytes]
+
+
+def jpeg_pixels_host(coef, geom):
+    """HOST statement of jpeg_pixels: coefficient buffer -> BGR uint8 numpy [h,w,3] (the arithmetic header the kernels compile)."""
+    w, h = int(geom[0]), int(geom[1])
+    assert not coef.is_cuda and coef.dtype == torch.uint8 and coef.is_contiguous() and coef.numel() >= jpeg_coef_bytes(geom)
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    rc = lib().frcnn_jpeg_pixels_host(coef.data_ptr(), w, h, int(geom[2]), int(geom[3]), int(geom[4]), out.ctypes.data)
+    if rc != 0:
+        raise JpegError("frcnn_jpeg_pixels_host", rc)
+    return out
+
+
+def jpeg_pixels(coef_d, geom, out=None):
+    """coef_d: the coefficient buffer on the device (uint8) -> BGR uint8 [h,w,3] on the device: IDCT into sample planes, then chroma
+    upsampling + colour conversion, on the current stream."""
+    w, h = int(geom[0]), int(geom[1])
+    assert coef_d.is_cuda and coef_d.dtype == torch.uint8 and coef_d.is_contiguous() and coef_d.numel() >= jpeg_coef_bytes(geom)
+    out = _empty((h, w, 3), dtype=torch.uint8, device=coef_d.device) if out is None else out
+    assert out.shape == (h, w, 3) and out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
+    ws = workspace(int(lib().frcnn_jpeg_workspace_bytes(w, h, int(geom[2]), int(geom[3]), int(geom[4]))), coef_d.device, tag="jpeg")
+    call("frcnn_jpeg_pixels", _ptr(coef_d), w, h, int(geom[2]), int(geom[3]), int(geom[4]), _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
 def winograd_filter_transform(w_hwio, scale=None, m=2):
     """HOST: 3x3 HWIO filter -> U [(m+2)^2, Cout, Cin] (F(m x m,3x3), optional folded per-output scale)."""
     w = np.ascontiguousarray(w_hwio, dtype=np.float32)

@@ -128,12 +128,16 @@ __C = AttrDict(
     # buffers are kept; the least recently used shape is dropped first and its buffers go back to the allocator (Session.shape_scope).  The
     # reference's graph takes any [1, H, W, 3] (lib/nets/network.py:386-390) and an imdb has hundreds of sizes: memory is bounded by these
     # caps, not by the imdb.  ResNet-101 at 600 x 1000 holds ~2 GB per shape.
+    # JPEG_DEVICE: the images of an imdb (model.test.imdb_images, roi_data_layer) are decoded by frcnn_hip.jpeg -- Huffman stage on host worker
+    # threads, IDCT + colour in two kernels, the same pixels as PIL bit for bit -- instead of PIL on the consuming thread; files the decoder
+    # does not take (progressive, CMYK, PNG, damaged) still go through PIL.  detect_bgr over JPEG files: 155 -> 219 images/s (profiles/jpeg_decode.txt);
+    # off by default, so that nothing changes unless it is asked for (--set HIP.JPEG_DEVICE True).
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
-             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16))
+             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False))
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))
 cfg = __C
 

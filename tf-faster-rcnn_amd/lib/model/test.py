@@ -96,7 +96,13 @@ def apply_nms(all_boxes, thresh):
 
 def imdb_images(imdb):
     """BGR uint8 images of an imdb (datasets.pascal_voc), decoded with PIL (cv2 is not available here; both wrap libjpeg, the
-    decoded pixels may differ in the last bit from cv2.imread's)."""
+    decoded pixels may differ in the last bit from cv2.imread's).  cfg.HIP.JPEG_DEVICE: the same pixels as device tensors from a
+    frcnn_hip.jpeg.JpegPrefetcher (host Huffman stage on worker threads, IDCT + colour on the device; detect_bgr takes either)."""
+    if cfg.HIP.JPEG_DEVICE:
+        from frcnn_hip.jpeg import JpegPrefetcher
+        for im in JpegPrefetcher([imdb.image_path_at(i) for i in range(imdb.num_images)], torch.device("cuda", torch.cuda.current_device())):
+            yield im
+        return
     from PIL import Image
     for i in range(imdb.num_images):
         yield np.ascontiguousarray(np.asarray(Image.open(imdb.image_path_at(i)).convert("RGB"))[:, :, ::-1])

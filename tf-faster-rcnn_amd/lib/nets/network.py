@@ -752,7 +752,7 @@ class Network(object):
             cap = max(self.TRAIN_MAX_GT, (G + 63) // 64 * 64)
             self._image = sess.buf(self._tag + "/image", (1, OH, OW, 4), zero=True)
             buf = sess.buf(self._tag + "/gt_boxes", (cap, 5), zero=True)
-            im_d = torch.from_numpy(np.ascontiguousarray(im)).to(dev, non_blocking=True)
+            im_d = (im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))).to(dev, non_blocking=True)   # cfg.HIP.JPEG_DEVICE: decoded there
             boxes_d = torch.from_numpy(np.ascontiguousarray(blobs["boxes"], dtype=np.uint16)).to(dev, non_blocking=True) if G else None
             classes_d = torch.from_numpy(np.ascontiguousarray(blobs["gt_classes"], dtype=np.int32)).to(dev, non_blocking=True) if G else None
             ops.prep_train_image(im_d, bool(blobs["flipped"]), cfg.PIXEL_MEANS, im_scale, (OH, OW), out=self._image, out_c=4,

@@ -24,6 +24,7 @@ class RoIDataLayer(object):
         self._rank, self._world_size = int(rank), int(world_size)
         self._count = 0                              # minibatches drawn from the stream so far, whichever rank they belong to
         self.last_draw = None                        # (roidb index, scale index) of the minibatch forward() returned last
+        self._jpeg = None                            # cfg.HIP.JPEG_DEVICE: a frcnn_hip.jpeg.JpegCache decoding the next entries ahead
         self._shuffle_roidb_inds()
 
     def _shuffle_roidb_inds(self):
@@ -66,7 +67,29 @@ class RoIDataLayer(object):
             if mine:
                 break
         self.last_draw = (int(db_inds[0]), int(scale_inds[0]))
-        return get_minibatch([self._roidb[i] for i in db_inds], self._num_classes, scale_inds)
+        return get_minibatch([self._roidb[i] for i in db_inds], self._num_classes, scale_inds,
+                             image=self._decoded(db_inds) if cfg.HIP.JPEG_DEVICE else None)
+
+    JPEG_AHEAD = 4                                   # entries of the permutation decoded ahead (host Huffman stage on worker threads)
+
+    def _decoded(self, db_inds):
+        """The image of this minibatch as a device tensor, and the Huffman stage of this rank's next entries of the CURRENT permutation
+        started on worker threads (peeked: nothing is drawn from the random stream; the entries after a reshuffle are not known yet)."""
+        import torch
+        from frcnn_hip.jpeg import JpegCache
+        if self._jpeg is None:
+            self._jpeg = JpegCache(torch.device("cuda", torch.cuda.current_device()), workers=4, depth=2 * self.JPEG_AHEAD)
+        path = self._roidb[int(db_inds[0])]['image']
+        im = self._jpeg.get(path, path)
+        step = cfg.TRAIN.IMS_PER_BATCH
+        pos = self._cur + ((self._rank - self._count) % self._world_size) * step
+        for _ in range(self.JPEG_AHEAD):
+            if pos + step >= len(self._roidb):       # that draw reshuffles first
+                break
+            nxt = self._roidb[int(self._perm[pos])]['image']
+            self._jpeg.prefetch(nxt, nxt)
+            pos += self._world_size * step
+        return im
 
     def __iter__(self):
         return self

@@ -1,8 +1,8 @@
 """roi_data_layer.minibatch -- one training minibatch from one roidb entry (lib/roi_data_layer/minibatch.py:19-74).
 
 The reference decodes, mirrors, mean-subtracts and resizes the image on the host (cv2) and returns the float `data` blob.  Here the
-resize is a device kernel (frcnn_prep_train_image), so the blob carries the RAW image instead -- `image` uint8 BGR [h,w,3] as decoded,
-`flipped`, `target_size`, `max_size` -- plus the roidb's `boxes` uint16 / `gt_classes` int32 rows the kernel turns into the device gt
+resize is a device kernel (frcnn_prep_train_image), so the blob carries the RAW image instead -- `image` uint8 BGR [h,w,3] as decoded (numpy; a device tensor under
+cfg.HIP.JPEG_DEVICE), `flipped`, `target_size`, `max_size` -- plus the roidb's `boxes` uint16 / `gt_classes` int32 rows the kernel turns into the device gt
 buffer.  `im_info` and `gt_boxes` are the reference's arrays (nets.network stages the blob: Network._stage_train_inputs)."""
 import numpy as np
 import numpy.random as npr
@@ -21,7 +21,15 @@ def draw_scales(num_images):
     return npr.randint(0, high=len(cfg.TRAIN.SCALES), size=num_images)
 
 
-def get_minibatch(roidb, num_classes, scale_inds=None):
+def read_image_device(path):
+    """cfg.HIP.JPEG_DEVICE: the same pixels as a uint8 device tensor (frcnn_hip.jpeg: host Huffman stage, IDCT + colour kernels)."""
+    import torch
+    from frcnn_hip.jpeg import decode_bgr
+    return decode_bgr(path, torch.device("cuda", torch.cuda.current_device()))
+
+
+def get_minibatch(roidb, num_classes, scale_inds=None, image=None):
+    """image: the entry's decoded image when the caller already has it (RoIDataLayer's prefetch under cfg.HIP.JPEG_DEVICE)."""
     from frcnn_hip import ops
     num_images = len(roidb)
     if scale_inds is None:
@@ -29,7 +37,10 @@ def get_minibatch(roidb, num_classes, scale_inds=None):
     assert cfg.TRAIN.BATCH_SIZE % num_images == 0, 'num_images ({}) must divide BATCH_SIZE ({})'.format(num_images, cfg.TRAIN.BATCH_SIZE)
     assert num_images == 1, "Single batch only"
     entry = roidb[0]
-    im = read_image(entry['image'])
+    if image is not None:
+        im = image
+    else:
+        im = read_image_device(entry['image']) if cfg.HIP.JPEG_DEVICE else read_image(entry['image'])
     target_size = int(cfg.TRAIN.SCALES[scale_inds[0]])
     im_scale, OH, OW = ops.prep_image_shape(im.shape[0], im.shape[1], target_size, cfg.TRAIN.MAX_SIZE)      # blob.py:37-45
     # minibatch.py:38-43: USE_ALL_GT or not, the reference's expression selects gt_classes != 0 (`0 & ...` binds first in the crowd branch)

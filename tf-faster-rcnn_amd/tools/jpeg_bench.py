@@ -1,0 +1,188 @@
+#!/usr/bin/env python
+"""Measurements behind cfg.HIP.JPEG_DEVICE (profiles/jpeg_decode.txt); separate from bench.py.
+
+Seeded 375 x 500 and 480 x 640 images at quality 90 in 4:2:0 / 4:2:2 / 4:4:4.  Old and new paths alternate inside one call, after a
+warm-up, with a few hundred decodes per timing window.
+
+  --host      ms per image on the host: PIL decode + [:, :, ::-1] copy (the path before) against frcnn_jpeg_entropy_decode alone,
+              one thread and 4 threads.  Needs no GPU.
+  --kernels   N runs of frcnn_jpeg_pixels per case on the device, nothing else: the process to put under
+              `rocprofv3 --kernel-trace --stats -- python tools/jpeg_bench.py --kernels`; prints the algorithmic bytes per image.
+  --e2e       images per second of model.test.detect_bgr over 200 JPEG files with cfg.HIP.JPEG_DEVICE off and on, alternated in one
+              process, three repeats each.
+"""
+import argparse
+import io
+import os
+import sys
+import tempfile
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+import _init_paths  # noqa: F401
+
+SIZES = ((375, 500), (480, 640))
+SAMPLINGS = ((2, "4:2:0"), (1, "4:2:2"), (0, "4:4:4"))
+
+
+def picture(h, w, seed):
+    from PIL import Image
+    rng = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    chans = [128 + 90 * np.sin(xx / (30.0 + 9 * c) + c) * np.cos(yy / (50.0 - 7 * c)) + 30 * np.sin((xx + yy) / 110.0) + rng.randn(h, w) * 12
+             for c in range(3)]
+    return Image.fromarray(np.clip(np.stack(chans, axis=2), 0, 255).astype(np.uint8), "RGB")
+
+
+def encode(im, sampling):
+    f = io.BytesIO()
+    im.save(f, "JPEG", quality=90, subsampling=sampling)
+    return f.getvalue()
+
+
+def pil_bgr(data):
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))[:, :, ::-1])
+
+
+def window(fn, n, threads):
+    """seconds per call of fn over n calls on `threads` threads"""
+    t0 = time.perf_counter()
+    if threads == 1:
+        for _ in range(n):
+            fn()
+    else:
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            list(ex.map(lambda _: fn(), range(n)))
+    return (time.perf_counter() - t0) / n
+
+
+def host(args):
+    import torch
+    from frcnn_hip import ops
+    print("host ms per image, %d decodes per window, %d alternated windows each (min / median)" % (args.n, args.windows))
+    print("%-9s %-6s %9s | %-15s | %-15s | %-15s" % ("size", "chroma", "bytes", "PIL+BGR 1 thr", "entropy 1 thr", "entropy 4 thr"))
+    for (h, w) in SIZES:
+        for sampling, label in SAMPLINGS:
+            data = encode(picture(h, w, h + sampling), sampling)
+            geom = ops.jpeg_info(data)
+            nbytes = ops.jpeg_coef_bytes(geom)
+            local = threading.local()                            # one coefficient buffer per thread
+
+            def entropy():
+                if not hasattr(local, "buf"):
+                    local.buf = torch.empty(nbytes, dtype=torch.uint8)
+                ops.jpeg_entropy_decode(data, out=local.buf, geom=geom)
+
+            def pil():
+                pil_bgr(data)
+            for fn in (pil, entropy):
+                window(fn, 20, 1)
+            res = {"pil": [], "e1": [], "e4": []}
+            for _ in range(args.windows):
+                res["pil"].append(window(pil, args.n, 1))
+                res["e1"].append(window(entropy, args.n, 1))
+                res["e4"].append(window(entropy, args.n, 4))
+            cell = lambda v: "%6.3f / %6.3f" % (min(v) * 1e3, float(np.median(v)) * 1e3)
+            print("%-9s %-6s %9d | %-15s | %-15s | %-15s" % ("%dx%d" % (h, w), label, len(data), cell(res["pil"]), cell(res["e1"]), cell(res["e4"])))
+
+
+def kernels(args):
+    import torch
+    from frcnn_hip import ops
+    dev = torch.device("cuda", 0)
+    for (h, w) in SIZES:
+        for sampling, label in SAMPLINGS:
+            data = encode(picture(h, w, h + sampling), sampling)
+            geom = ops.jpeg_info(data)
+            coef_d = ops.jpeg_entropy_decode(data, geom=geom).to(dev)
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+            planes = int(ops.lib().frcnn_jpeg_workspace_bytes(*geom[:5]))
+            for _ in range(args.n):
+                ops.jpeg_pixels(coef_d, geom, out=out)
+            torch.cuda.synchronize()
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for _ in range(args.n):
+                ops.jpeg_pixels(coef_d, geom, out=out)
+            ev1.record()
+            torch.cuda.synchronize()
+            print("%dx%d %s: coefficients in %d B, planes out and in 2 x %d B, BGR out %d B = %d algorithmic bytes per image; "
+                  "%.2f us per image between events (two launches, back to back, %d images)"
+                  % (h, w, label, coef_d.numel(), planes, h * w * 3, coef_d.numel() + 2 * planes + h * w * 3,
+                     ev0.elapsed_time(ev1) * 1e3 / args.n, args.n))
+
+
+def e2e(args):
+    import torch
+    from frcnn_hip.jpeg import JpegPrefetcher
+    from frcnn_hip.runtime import Session
+    from model.config import cfg
+    from model.test import detect_bgr
+    from nets.resnet_v1 import resnetv1
+    torch.cuda.set_device(0)
+    sess = Session(seed=3)
+    net = resnetv1(num_layers=args.layers)
+    net.create_architecture("TEST", 21, tag="default", anchor_scales=cfg.ANCHOR_SCALES, anchor_ratios=cfg.ANCHOR_RATIOS)
+    sess.init_variables(net.variable_specs())
+    tmp = tempfile.mkdtemp(prefix="jpeg_bench_")
+    paths = []
+    for i in range(args.files):
+        h, w = SIZES[i % 2]
+        p = os.path.join(tmp, "%04d.jpg" % i)
+        with open(p, "wb") as f:
+            f.write(encode(picture(h, w, i), SAMPLINGS[i % 3][0]))
+        paths.append(p)
+
+    def run(on):
+        t0 = time.perf_counter()
+        if on:
+            for im in JpegPrefetcher(paths, sess.device):
+                detect_bgr(sess, net, im)
+        else:
+            for p in paths:
+                with open(p, "rb") as f:
+                    detect_bgr(sess, net, pil_bgr(f.read()))
+        torch.cuda.synchronize()
+        return len(paths) / (time.perf_counter() - t0)
+    run(False), run(True)                                       # warm-up: graphs of both shapes, pinned buffers, file cache
+    res = {False: [], True: []}
+    for _ in range(3):
+        for on in (False, True):
+            res[on].append(run(on))
+    print("detect_bgr over %d JPEG files (375x500 / 480x640 alternating, 4:2:0 / 4:2:2 / 4:4:4, quality 90), ResNet-%d, images per second, "
+          "three alternated repeats" % (len(paths), args.layers))
+    for on in (False, True):
+        v = res[on]
+        print("  JPEG_DEVICE %-5s: %s  (min %.1f, max %.1f)" % (on, "  ".join("%.1f" % x for x in v), min(v), max(v)))
+    for p in paths:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--n", type=int, default=300, help="decodes per timing window / launches per case")
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--files", type=int, default=200)
+    ap.add_argument("--layers", type=int, default=101)
+    args = ap.parse_args(argv)
+    if not (args.host or args.kernels or args.e2e):
+        ap.error("one of --host / --kernels / --e2e")
+    if args.host:
+        host(args)
+    if args.kernels:
+        kernels(args)
+    if args.e2e:
+        e2e(args)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

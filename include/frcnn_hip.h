@@ -273,6 +273,11 @@ long long frcnn_snappy_uncompress(const unsigned char* src, size_t n, unsigned c
 int frcnn_prep_image_shape(int h, int w, int target_size, int max_size, double* im_scale, int* out_h, int* out_w);
 int frcnn_prep_image(const void* src_d, int src_is_float, int h, int w, const double* pixel_means, double im_scale, float* out_d,
                      int OH, int OW, int out_c, void* stream);
+/* frcnn_prep_image of B same-size images in one launch (the image index on gridDim.z): src_d [B][h][w][3] -> out_d [B][OH][OW][out_c],
+ * slot b bit-identical to frcnn_prep_image of image b (one __device__ function holds the arithmetic of both kernels).  B <= 0 or
+ * B > 65535: FRCNN_E_ARG. */
+int frcnn_prep_image_batched(const void* src_d, int src_is_float, int B, int h, int w, const double* pixel_means, double im_scale,
+                             float* out_d, int OH, int OW, int out_c, void* stream);
 /* The training minibatch of one roidb entry on device (lib/roi_data_layer/minibatch.py:19-74, lib/utils/blob.py:33-47):
  * frcnn_prep_image with the source mirrored first iff `flipped` (im[:, ::-1, :]: column x is read at w-1-x), plus rows [0,G) of
  * the static gt buffer gt_d [>=G][5] from the entry's boxes_d uint16 [G][4] and classes_d int32 [G]: coordinate =

@@ -32,11 +32,10 @@ struct Mean3 { double b, g, r; };
 // FLIP: the source is read mirrored (minibatch.py:63-64 `im[:, ::-1, :]` before anything else): mirrored column x is stored column
 // w-1-x.  The tap arithmetic is unchanged, so a wave still reads its taps from the same few cache lines, in descending order.
 // VEC4 (OC == 4 and a 16-byte aligned output, chosen by the launcher): one 16-byte store per lane, a wave writes 1 KiB contiguous.
+// One output pixel (ox, oy) of one image: the arithmetic of k_prep_image and k_prep_image_batched, stated once.
 template <typename SRC, bool FLIP, bool VEC4>
-__global__ void k_prep_image(const SRC* __restrict__ src, int h, int w, Mean3 mean, double scale_inv, int OH, int OW, int OC,
-                             float* __restrict__ out) {
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
-  if (ox >= OW) return;
+__device__ __forceinline__ void prep_pixel(const SRC* __restrict__ src, int h, int w, Mean3 mean, double scale_inv, int OW, int OC,
+                                           int ox, int oy, float* __restrict__ out) {
   float fx = (float)(((double)ox + 0.5) * scale_inv - 0.5);
   int sx = (int)floorf(fx);
   fx -= (float)sx;
@@ -75,6 +74,23 @@ __global__ void k_prep_image(const SRC* __restrict__ src, int h, int w, Mean3 me
   }
 }
 
+template <typename SRC, bool FLIP, bool VEC4>
+__global__ void k_prep_image(const SRC* __restrict__ src, int h, int w, Mean3 mean, double scale_inv, int OH, int OW, int OC,
+                             float* __restrict__ out) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+  if (ox >= OW) return;
+  prep_pixel<SRC, FLIP, VEC4>(src, h, w, mean, scale_inv, OW, OC, ox, oy, out);
+}
+
+// B same-size images in one launch: image b = blockIdx.z reads src[b][h][w][3] and writes out[b][OH][OW][OC].
+template <typename SRC, bool VEC4>
+__global__ void k_prep_image_batched(const SRC* __restrict__ src, int h, int w, Mean3 mean, double scale_inv, int OH, int OW, int OC,
+                                     float* __restrict__ out) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, b = blockIdx.z;
+  if (ox >= OW) return;
+  prep_pixel<SRC, false, VEC4>(src + (size_t)b * h * w * 3, h, w, mean, scale_inv, OW, OC, ox, oy, out + (size_t)b * OH * OW * OC);
+}
+
 template <typename SRC, bool FLIP>
 static void launch_prep(const void* src_d, int h, int w, const double* pixel_means, double im_scale, float* out_d, int OH, int OW, int out_c,
                         hipStream_t stream) {
@@ -96,6 +112,33 @@ extern "C" int frcnn_prep_image(const void* src_d, int src_is_float, int h, int 
     launch_prep<float, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
   else
     launch_prep<unsigned char, false>(src_d, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+template <typename SRC>
+static void launch_prep_batched(const void* src_d, int B, int h, int w, const double* pixel_means, double im_scale, float* out_d, int OH,
+                                int OW, int out_c, hipStream_t stream) {
+  const Mean3 mean = {pixel_means[0], pixel_means[1], pixel_means[2]};
+  const dim3 grid((OW + 255) / 256, OH, B), block(256);
+  // a slot starts OH * OW * 16 bytes after the one before: every slot is 16-byte aligned iff the first is -- frcnn_prep_image's condition
+  if (out_c == 4 && ((size_t)out_d & 15) == 0)
+    hipLaunchKernelGGL((k_prep_image_batched<SRC, true>), grid, block, 0, stream, (const SRC*)src_d, h, w, mean, 1.0 / im_scale, OH, OW, out_c, out_d);
+  else
+    hipLaunchKernelGGL((k_prep_image_batched<SRC, false>), grid, block, 0, stream, (const SRC*)src_d, h, w, mean, 1.0 / im_scale, OH, OW, out_c, out_d);
+}
+
+// frcnn_prep_image of B same-size images in ONE launch (the image index on gridDim.z; B <= 65535, OH <= 65535: the grid's limits):
+// src_d [B][h][w][3] -> out_d [B][OH][OW][out_c], slot b bit-identical to frcnn_prep_image of image b (both kernels call prep_pixel).
+extern "C" int frcnn_prep_image_batched(const void* src_d, int src_is_float, int B, int h, int w, const double* pixel_means, double im_scale,
+                                        float* out_d, int OH, int OW, int out_c, void* stream) {
+  if (!src_d || !pixel_means || !out_d || B <= 0 || h <= 0 || w <= 0 || OH <= 0 || OW <= 0 || !(im_scale > 0)) return FRCNN_E_ARG;
+  if (B > 65535 || OH > 65535) return FRCNN_E_ARG;
+  if (out_c != 3 && out_c != 4) return FRCNN_E_UNSUPPORTED;
+  if (src_is_float)
+    launch_prep_batched<float>(src_d, B, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
+  else
+    launch_prep_batched<unsigned char>(src_d, B, h, w, pixel_means, im_scale, out_d, OH, OW, out_c, (hipStream_t)stream);
   LAUNCH_CHECK();
   return FRCNN_OK;
 }

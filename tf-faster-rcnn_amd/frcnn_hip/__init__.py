@@ -74,6 +74,7 @@ SIGNATURES = {
     "frcnn_snappy_uncompress": (c_longlong, [_P, c_size_t, _P, c_size_t]),
     "frcnn_prep_image_shape": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P]),
     "frcnn_prep_image": (c_int, [_P, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P]),
+    "frcnn_prep_image_batched": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P]),
     "frcnn_prep_train_image": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_double, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "frcnn_jpeg_info": (c_int, [_P, c_size_t, _P]),
     "frcnn_jpeg_coef_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -37,17 +37,34 @@ def _is_cuda(device):
     return torch.device(device).type == "cuda"
 
 
-def decode_bgr(src, device):
-    """File path or bytes -> BGR uint8 [h,w,3] tensor on `device`.  device 'cpu': the host statement of the kernels."""
+def _into(t, out):
+    """t, or `out` holding t's pixels (a caller's slot of a batch buffer; the shapes must agree)"""
+    if out is None:
+        return t
+    out.copy_(t, non_blocking=True)
+    return out
+
+
+def _pixels(coef_d, geom, out):
+    """ops.jpeg_pixels into `out` directly where the colour kernel's dword stores allow it (a 4-byte aligned address; slot k of a batch
+    buffer starts k * h * w * 3 bytes in, which is not one when h * w is no multiple of 4), else into a tensor of its own and a copy"""
+    if out is None or out.data_ptr() % 4 == 0:
+        return ops.jpeg_pixels(coef_d, geom, out=out)
+    return _into(ops.jpeg_pixels(coef_d, geom), out)
+
+
+def decode_bgr(src, device, out=None):
+    """File path or bytes -> BGR uint8 [h,w,3] tensor on `device`.  device 'cpu': the host statement of the kernels.
+    out: a [h,w,3] uint8 tensor on `device` to decode into (the kernels write it directly where its address is 4-byte aligned)."""
     data = _read(src)
     try:
         geom = ops.jpeg_info(data)
         coef = ops.jpeg_entropy_decode(data, geom=geom)
     except ops.JpegError:
-        return torch.from_numpy(pil_bgr(src)).to(device)
+        return _into(torch.from_numpy(pil_bgr(src)).to(device), out)
     if not _is_cuda(device):
-        return torch.from_numpy(ops.jpeg_pixels_host(coef, geom))
-    return ops.jpeg_pixels(coef.to(device), geom)
+        return _into(torch.from_numpy(ops.jpeg_pixels_host(coef, geom)), out)
+    return _pixels(coef.to(device), geom, out)
 
 
 class _Slot(object):
@@ -59,7 +76,7 @@ class _Slot(object):
 
 class JpegCache(object):
     """prefetch(key, src) starts reading + entropy-decoding `src` on a worker thread if one of the `depth` pinned buffers is free;
-    get(key, src) returns the device tensor (decoding synchronously what was never prefetched)."""
+    get(key, src) returns the device tensor (decoding synchronously what was never prefetched), `out` given: that tensor, written directly."""
 
     MIN_SLOT_BYTES = 1 << 20         # a 480 x 640 4:2:0 image needs 0.46 MB: most slots are allocated once
 
@@ -98,23 +115,23 @@ class JpegCache(object):
         self._pending[key] = (self._pool.submit(self._work, src, k), k)
         return True
 
-    def get(self, key, src):
+    def get(self, key, src, out=None):
         if key not in self._pending:
-            return decode_bgr(src, self.device)
+            return decode_bgr(src, self.device, out)
         fut, k = self._pending.pop(key)
         try:
             res = fut.result()
             if res[0] == "pil":
-                return torch.from_numpy(res[1]).to(self.device, non_blocking=True)
+                return _into(torch.from_numpy(res[1]).to(self.device, non_blocking=True), out)
             _, geom, coef = res
             if not self._cuda:
-                return torch.from_numpy(ops.jpeg_pixels_host(coef, geom))
+                return _into(torch.from_numpy(ops.jpeg_pixels_host(coef, geom)), out)
             coef_d = coef.to(self.device, non_blocking=True)
             slot = self._slots[k]
             if slot.ev is None:
                 slot.ev = torch.cuda.Event()
             slot.ev.record(torch.cuda.current_stream())
-            return ops.jpeg_pixels(coef_d, geom)
+            return _pixels(coef_d, geom, out)
         finally:
             self._free.append(k)
 
@@ -149,17 +166,21 @@ class JpegPrefetcher(object):
         return self
 
     def __next__(self):
+        return self.read_into(None)
+
+    next = __next__
+
+    def read_into(self, out):
+        """the next image decoded INTO `out` ([h,w,3] uint8 on the device, e.g. one slot of a batch buffer); None: a new tensor"""
         if self._i >= len(self._paths):
             self._cache.close()
             raise StopIteration
         i = self._i
         self._i += 1
         try:
-            return self._cache.get(i, self._paths[i])
+            return self._cache.get(i, self._paths[i], out)
         finally:
             self._fill()
-
-    next = __next__
 
     def close(self):
         self._cache.close()

@@ -527,6 +527,21 @@ def prep_image(im_d, pixel_means, im_scale, out_hw, out=None, out_c=4):
     return out
 
 
+def prep_image_batched(ims_d, pixel_means, im_scale, out_hw, out=None, out_c=4):
+    """ims_d: B same-size BGR images, uint8 or float32 [B,h,w,3] on device -> float32 [B,OH,OW,out_c] in one launch; slot b holds the bits
+    of prep_image(ims_d[b])."""
+    assert ims_d.is_cuda and ims_d.is_contiguous() and ims_d.dim() == 4 and ims_d.shape[3] == 3 and ims_d.shape[0] >= 1
+    assert ims_d.dtype in (torch.uint8, torch.float32)
+    B, h, w = ims_d.shape[:3]
+    OH, OW = out_hw
+    out = _empty((B, OH, OW, out_c), dtype=torch.float32, device=ims_d.device) if out is None else out
+    assert out.shape == (B, OH, OW, out_c) and out.is_contiguous() and out.dtype == torch.float32
+    means = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(pixel_means, dtype=np.float64).reshape(-1)[:3]])
+    call("frcnn_prep_image_batched", _ptr(ims_d), 1 if ims_d.dtype == torch.float32 else 0, B, h, w, means, float(im_scale), _ptr(out), OH,
+         OW, int(out_c), _stream())
+    return out
+
+
 def prep_train_image(im_d, flipped, pixel_means, im_scale, out_hw, out=None, out_c=4, boxes=None, classes=None, gt_out=None):
     """One roidb entry's minibatch on device (roi_data_layer/minibatch.py): prep_image of the image mirrored first iff `flipped`, and --
     boxes uint16 [G,4] / classes int32 [G] / gt_out float32 [>=G,5] given -- gt_out[:G] = (boxes * im_scale, classes)."""

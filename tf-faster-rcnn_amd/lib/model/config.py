@@ -132,12 +132,17 @@ __C = AttrDict(
     # threads, IDCT + colour in two kernels, the same pixels as PIL bit for bit -- instead of PIL on the consuming thread; files the decoder
     # does not take (progressive, CMYK, PNG, damaged) still go through PIL.  detect_bgr over JPEG files: 155 -> 219 images/s (profiles/jpeg_decode.txt);
     # off by default, so that nothing changes unless it is asked for (--set HIP.JPEG_DEVICE True).
+    # TEST_BATCH_IMAGES: model.test.test_net_imdb runs same-size images of the imdb this many per launch (plan_batches groups them by source size
+    # from the file headers; frcnn_prep_image_batched stages a batch in one launch; a batch's detections are read back after the next batch
+    # has been enqueued).  all_boxes is the one-by-one loop's, array for array.  A run without a limit per image (max_per_image <= 0) keeps
+    # the one-by-one loop: the batched one reads back a fixed-size record per image.  Measurements: profiles/test_net_batched.txt; 1 = the loop
+    # as it was, the default, so that nothing changes unless it is asked for (--set HIP.TEST_BATCH_IMAGES 8).
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
-             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False))
+             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1))
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))
 cfg = __C
 

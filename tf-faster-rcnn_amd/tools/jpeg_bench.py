@@ -9,7 +9,9 @@ warm-up, with a few hundred decodes per timing window.
   --kernels   N runs of frcnn_jpeg_pixels per case on the device, nothing else: the process to put under
               `rocprofv3 --kernel-trace --stats -- python tools/jpeg_bench.py --kernels`; prints the algorithmic bytes per image.
   --e2e       images per second of model.test.detect_bgr over 200 JPEG files with cfg.HIP.JPEG_DEVICE off and on, alternated in one
-              process, three repeats each.
+              process, three repeats each.  --batch N [N ...]: the same files through model.test.detect_paths_batched (the loop of
+              test_net_imdb under cfg.HIP.TEST_BATCH_IMAGES = N; 1 = the detect_bgr loop above), every (N, switch) pair alternated in
+              the same process (profiles/test_net_batched.txt).
 """
 import argparse
 import io
@@ -118,10 +120,8 @@ def kernels(args):
 
 def e2e(args):
     import torch
-    from frcnn_hip.jpeg import JpegPrefetcher
     from frcnn_hip.runtime import Session
     from model.config import cfg
-    from model.test import detect_bgr
     from nets.resnet_v1 import resnetv1
     torch.cuda.set_device(0)
     sess = Session(seed=3)
@@ -137,9 +137,31 @@ def e2e(args):
             f.write(encode(picture(h, w, i), SAMPLINGS[i % 3][0]))
         paths.append(p)
 
-    def run(on):
+    saved = (cfg.HIP.JPEG_DEVICE, cfg.HIP.GRAPH_CACHE_SHAPES)           # the runs set both: main(argv) leaves the caller's cfg as it found it
+    try:
+        _e2e_runs(args, sess, net, paths)
+    finally:
+        cfg.HIP.JPEG_DEVICE, cfg.HIP.GRAPH_CACHE_SHAPES = saved
+        for p in paths:
+            os.remove(p)
+        os.rmdir(tmp)
+
+
+def _e2e_runs(args, sess, net, paths):
+    import torch
+    from frcnn_hip.jpeg import JpegPrefetcher
+    from model.config import cfg
+    from model.test import detect_bgr, detect_paths_batched
+    # every (batch, shape) pair keeps its graph while the settings alternate: no timed window re-captures one (a test_net run has one batch
+    # size, i.e. at most two graphs per shape, used in one contiguous stretch)
+    cfg.HIP.GRAPH_CACHE_SHAPES = max(int(cfg.HIP.GRAPH_CACHE_SHAPES), len(SIZES) * 2 * len(args.batch))
+
+    def run(on, batch):
         t0 = time.perf_counter()
-        if on:
+        if batch > 1:
+            cfg.HIP.JPEG_DEVICE = on
+            detect_paths_batched(sess, net, paths, batch)
+        elif on:
             for im in JpegPrefetcher(paths, sess.device):
                 detect_bgr(sess, net, im)
         else:
@@ -148,19 +170,54 @@ def e2e(args):
                     detect_bgr(sess, net, pil_bgr(f.read()))
         torch.cuda.synchronize()
         return len(paths) / (time.perf_counter() - t0)
-    run(False), run(True)                                       # warm-up: graphs of both shapes, pinned buffers, file cache
-    res = {False: [], True: []}
+    cases = [(on, b) for b in args.batch for on in (False, True)]
+    for on, b in cases:                                         # warm-up: graphs of every (batch, shape), pinned buffers, file cache
+        run(on, b)
+    res = {c: [] for c in cases}
     for _ in range(3):
-        for on in (False, True):
-            res[on].append(run(on))
+        for c in cases:
+            res[c].append(run(*c))
     print("detect_bgr over %d JPEG files (375x500 / 480x640 alternating, 4:2:0 / 4:2:2 / 4:4:4, quality 90), ResNet-%d, images per second, "
           "three alternated repeats" % (len(paths), args.layers))
-    for on in (False, True):
-        v = res[on]
-        print("  JPEG_DEVICE %-5s: %s  (min %.1f, max %.1f)" % (on, "  ".join("%.1f" % x for x in v), min(v), max(v)))
-    for p in paths:
-        os.remove(p)
-    os.rmdir(tmp)
+    for on, b in cases:
+        v = res[(on, b)]
+        print("  batch %d  JPEG_DEVICE %-5s: %s  (min %.1f, max %.1f)" % (b, on, "  ".join("%.1f" % x for x in v), min(v), max(v)))
+    if max(args.batch) > 1:
+        # what each stage of the batched loop sustains ALONE, same files, same process: the slowest one bounds the loop
+        from model import test as mt
+
+        def alone(fn):
+            fn()
+            v = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                v.append(len(paths) / (time.perf_counter() - t0))
+            return "  ".join("%.1f" % x for x in v)
+
+        def pil_only():
+            for p in paths:
+                pil_bgr(open(p, "rb").read())
+
+        def prefetch_only():
+            for _ in JpegPrefetcher(paths, sess.device):
+                pass
+        print("stages alone, images per second, three repeats:")
+        print("  PIL decode + BGR copy, one thread (JPEG_DEVICE False)      : %s" % alone(pil_only))
+        print("  JpegPrefetcher, 4 workers + copy + 2 launches (True)       : %s" % alone(prefetch_only))
+        for b in args.batch:
+            stages = [torch.randint(0, 256, (b, h, w, 3), dtype=torch.uint8, device=sess.device) for (h, w) in SIZES]
+
+            def chain_only():
+                ring, prev = mt._PinnedRing(2), None
+                for k in range(len(paths) // b):
+                    cur = mt._enqueue_batch(sess, net, stages[(k * b // (len(paths) // 2)) % 2], b, 100, 0., ring)
+                    if prev is not None:
+                        mt._finish_batch(prev)
+                    prev = cur
+                mt._finish_batch(prev)
+            print("  prep + chain + post + deferred read-back, batch %d, no decode : %s" % (b, alone(chain_only)))
 
 
 def main(argv=None):
@@ -172,6 +229,7 @@ def main(argv=None):
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--files", type=int, default=200)
     ap.add_argument("--layers", type=int, default=101)
+    ap.add_argument("--batch", type=int, nargs="+", default=[1], help="--e2e: same-size images per launch (1 = the detect_bgr loop)")
     args = ap.parse_args(argv)
     if not (args.host or args.kernels or args.e2e):
         ap.error("one of --host / --kernels / --e2e")

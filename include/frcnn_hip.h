@@ -581,6 +581,31 @@ int frcnn_sumsq(const float* w_d, long long n, double scale, float* out_d, int a
 int frcnn_sumsq_multi(const void* ptr_table_d, const long long* sizes_d, int count, double scale, float* out_d, int accumulate,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---- summary statistics (TensorBoard histograms: frcnn_hip/summary.py; additive, FRCNN_ABI_VERSION unchanged) ---------- */
+/* TensorFlow's default histogram bucket limits (core/lib/histogram/histogram.cc): 1e-12 * 1.1^k below 1e20 by repeated multiplication in
+ * double (774 values), then DBL_MAX; negated and reversed in front, 0.0 between.  bucket(x) = index of the first limit > (double)x.
+ * HOST: frcnn_summary_limits writes the 1551 limits the device kernel uses (one table for Python and the kernel). */
+#define FRCNN_SUMMARY_BUCKETS 1551
+/* One record per tensor, FRCNN_SUMMARY_RECORD 8-byte words: [0, 1551) int64 bucket counts, then int64 num (every element), n_zero
+ * (x == 0, either sign; also counted in bucket 776), n_nonfinite (NaN / +-inf: counted here ONLY -- no bucket, sum or extremum), then
+ * float64 min, max (over the finite values; DBL_MAX / -DBL_MAX when there is none), sum, sum_squares (float64 accumulation). */
+#define FRCNN_SUMMARY_NUM 1551
+#define FRCNN_SUMMARY_NZERO 1552
+#define FRCNN_SUMMARY_NNONFINITE 1553
+#define FRCNN_SUMMARY_MIN 1554
+#define FRCNN_SUMMARY_MAX 1555
+#define FRCNN_SUMMARY_SUM 1556
+#define FRCNN_SUMMARY_SUMSQ 1557
+#define FRCNN_SUMMARY_RECORD 1560
+int frcnn_summary_limits(double* out1551);
+size_t frcnn_summary_stats_workspace_bytes(int count);
+/* seg_table_d: device array of `count` rows { const float* ptr; long long n; } (ptr 4-byte aligned, any float offset into a buffer;
+ * n >= 0, below 2^38); out_d: count records as above (8-byte aligned), every word written.  Counts are exact; sum / sum_squares are
+ * folded in a fixed order (no float atomics): the same bytes on every run for the same pointers and counts.  Three enqueues for the
+ * whole table.  count == 0: FRCNN_OK, nothing enqueued; count > 65535: FRCNN_E_ARG; ws smaller than
+ * frcnn_summary_stats_workspace_bytes(count): FRCNN_E_WS, nothing enqueued. */
+int frcnn_summary_stats(const void* seg_table_d, int count, void* out_d, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- stream capture (one hipGraph per image-shape; replaces the per-image sess.run) ---------- */
 int frcnn_graph_begin(void* stream);
 int frcnn_graph_end(void* stream, void** graph_exec_out);

@@ -159,6 +159,9 @@ SIGNATURES = {
     "frcnn_sgd_momentum_range": (c_int, [_P, c_int, c_int, c_float, c_float, c_float, _P]),
     "frcnn_sumsq": (c_int, [_P, c_longlong, c_double, _P, c_int, _P, c_size_t, _P]),
     "frcnn_sumsq_multi": (c_int, [_P, _P, c_int, c_double, _P, c_int, _P, c_size_t, _P]),
+    "frcnn_summary_limits": (c_int, [_P]),
+    "frcnn_summary_stats_workspace_bytes": (c_size_t, [c_int]),
+    "frcnn_summary_stats": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
     "frcnn_graph_begin": (c_int, [_P]),
     "frcnn_graph_end": (c_int, [_P, ctypes.POINTER(c_void_p)]),
     "frcnn_graph_launch": (c_int, [_P, _P]),

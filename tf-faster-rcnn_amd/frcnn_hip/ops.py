@@ -1271,6 +1271,60 @@ def sumsq_multi(ptr_table, sizes, scale, out, accumulate=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------ summary statistics
+SUMMARY_BUCKETS, SUMMARY_RECORD = 1551, 1560          # include/frcnn_hip.h FRCNN_SUMMARY_*: words 1551.. = num, n_zero, n_nonfinite, min, max, sum, sum_squares
+_summary_limits = None
+
+
+def summary_limits():
+    """HOST float64 [1551]: TensorFlow's default histogram bucket limits, the table the device kernel uses (frcnn_summary_limits)."""
+    global _summary_limits
+    if _summary_limits is None:
+        out = np.empty((SUMMARY_BUCKETS,), dtype=np.float64)
+        call("frcnn_summary_limits", out.ctypes.data_as(ctypes.c_void_p))
+        out.setflags(write=False)
+        _summary_limits = out
+    return _summary_limits
+
+
+class SummaryPlan(object):
+    """frcnn_summary_stats over a fixed list of device tensors (float32, contiguous; views at any float offset): the (pointer, count)
+    table, the record buffer and the scratch are made once, `launch()` is the three enqueues on the current stream, `read()` the one
+    read-back.  The plan holds addresses, not tensors: it is valid while the caller keeps them where they are (static step buffers, solver
+    state)."""
+
+    def __init__(self, tensors):
+        tensors = [_chk(t) for t in tensors]
+        self.count = len(tensors)
+        dev = tensors[0].device if tensors else None
+        if self.count:
+            self.table = torch.tensor([[t.data_ptr(), t.numel()] for t in tensors], dtype=torch.int64).to(dev)
+            self.out = torch.empty((self.count, SUMMARY_RECORD), dtype=torch.int64, device=dev)
+            self.ws = torch.empty((int(lib().frcnn_summary_stats_workspace_bytes(self.count)),), dtype=torch.uint8, device=dev)
+
+    def launch(self):
+        if self.count:
+            call("frcnn_summary_stats", _ptr(self.table), self.count, _ptr(self.out), _ptr(self.ws), self.ws.numel(), _stream())
+        return self
+
+    def read(self):
+        """list of dict(counts int64 [1551], num, n_zero, n_nonfinite, min, max, sum, sum_squares), one per tensor (waits for the launch)"""
+        if not self.count:
+            return []
+        raw = self.out.cpu().numpy()
+        f = raw.view(np.float64)
+        return [dict(counts=raw[i, :SUMMARY_BUCKETS].copy(), num=int(raw[i, 1551]), n_zero=int(raw[i, 1552]), n_nonfinite=int(raw[i, 1553]),
+                     min=float(f[i, 1554]), max=float(f[i, 1555]), sum=float(f[i, 1556]), sum_squares=float(f[i, 1557]))
+                for i in range(self.count)]
+
+
+def summary_stats(tensors):
+    """Histogram + moments of every tensor of the list in one launch sequence (csrc/summary_stats.hip) -> list of dict, see
+    SummaryPlan.read.  A non-finite value is counted in n_nonfinite only."""
+    tensors = list(tensors)                                  # (alive until the read-back)
+    return SummaryPlan(tensors).launch().read()
+
+
 class Graph:
     """One captured hipGraph (frcnn_graph_* in the C ABI)."""
 

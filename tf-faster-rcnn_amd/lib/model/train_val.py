@@ -9,8 +9,12 @@ trains on a single GPU with IMS_PER_BATCH 1).  Checkpoints are TensorFlow V2 bun
 (frcnn_hip/tensor_bundle.py): `initialize` = ImageNet weights + fix_variables (:177-202), `snapshot` = Saver.save of the
 variables, the Momentum slots and a `.pkl` with the iteration, the data layer's cursor / permutation and numpy's global random state
 (:58-100), `restore` (:204-233).  `get_training_roidb` / `filter_roidb` (:324-360) prepare a roidb for roi_data_layer.layer.RoIDataLayer.
-TensorBoard is out of scope; `data_layer` is any iterator of blobs {'data','im_info','gt_boxes'} (float image) or of
-RoIDataLayer's raw-image blobs (roi_data_layer/minibatch.py)."""
+TensorBoard (:149-151,281-290): with `tb_dir` the wrapper keeps a train writer and -- given `data_layer_val` -- a `<tb_dir>_val` writer
+(frcnn_hip/summary.py: event files written without TensorFlow) and summarises iteration 1 and then one iteration every
+cfg.TRAIN.SUMMARY_INTERVAL seconds: Network.train_step_with_summary (losses, ACT / SCORE / TRAIN histograms from the device statistics
+kernel, the ground-truth image) and Network.get_summary on a validation minibatch.  Every other iteration is the plain train_step_async;
+a summary changes no bit of the run (tests/test_summary_gpu.py).  Rank 0 only under data parallel (write_snapshots).  `data_layer` is any
+iterator of blobs {'data','im_info','gt_boxes'} (float image) or of RoIDataLayer's raw-image blobs (roi_data_layer/minibatch.py)."""
 import os
 import pickle
 import time
@@ -51,8 +55,12 @@ def remove_snapshot(np_paths, ss_paths):
 
 
 class SolverWrapper(object):
-    def __init__(self, sess, network, data_layer, all_reduce=None, world_size=1, write_snapshots=True, force_dp=False):
+    def __init__(self, sess, network, data_layer, all_reduce=None, world_size=1, write_snapshots=True, force_dp=False, tb_dir=None,
+                 data_layer_val=None):
         self.sess, self.net, self.data_layer = sess, network, data_layer
+        self.data_layer_val = data_layer_val
+        self.tb_dir = tb_dir if write_snapshots else None         # data-parallel runs: rank 0 writes the event files too
+        self.writer = self.valwriter = None                       # summary.FileWriter, opened by train_model
         self.write_snapshots = bool(write_snapshots)               # data-parallel runs: every rank READS snapshots, rank 0 writes them
         self.state = TrainState(sess, network, momentum=cfg.TRAIN.MOMENTUM, weight_decay=cfg.TRAIN.WEIGHT_DECAY,
                                 double_bias=cfg.TRAIN.DOUBLE_BIAS, bias_decay=cfg.TRAIN.BIAS_DECAY)
@@ -128,12 +136,24 @@ class SolverWrapper(object):
             self.ss_paths.append(sfile)
         return meta['iter']
 
+    def close_writers(self):
+        for w in (self.writer, self.valwriter):
+            if w is not None:
+                w.close()
+        self.writer = self.valwriter = None
+
     def train_model(self, max_iters, verbose=True, start_iter=0, snapshot_dir=None):
         lr = cfg.TRAIN.LEARNING_RATE
         stepsizes = sorted(cfg.TRAIN.STEPSIZE, reverse=True)
         next_stepsize = stepsizes.pop() if stepsizes else None
         history = []
         t0 = time.time()
+        if self.tb_dir is not None and self.writer is None:
+            from frcnn_hip.summary import FileWriter
+            self.writer = FileWriter(self.tb_dir)
+            if self.data_layer_val is not None:
+                self.valwriter = FileWriter(self.tb_dir + '_val')
+        last_summary_time = time.time()
         while next_stepsize is not None and start_iter > next_stepsize:          # resumed past a step: :225-231
             lr *= cfg.TRAIN.GAMMA
             next_stepsize = stepsizes.pop() if stepsizes else None
@@ -143,8 +163,20 @@ class SolverWrapper(object):
                 next_stepsize = stepsizes.pop() if stepsizes else None
             self.state.lr = lr
             blobs = next(self.data_layer)
-            # no host synchronisation inside a step: the losses stay on the device until somebody looks at them
-            history.append(self.net.train_step_async(self.sess, blobs, self.state))
+            now = time.time()
+            if self.writer is not None and (it == 1 or now - last_summary_time > cfg.TRAIN.SUMMARY_INTERVAL):      # :281-290
+                import torch
+                out = self.net.train_step_with_summary(self.sess, blobs, self.state)
+                history.append(torch.tensor(out[:5], dtype=torch.float32, device=self.sess.device))
+                self.writer.add_summary(out[5], it)
+                if self.valwriter is not None:
+                    self.valwriter.add_summary(self.net.get_summary(self.sess, next(self.data_layer_val), self.state), it)
+                    self.valwriter.flush()
+                self.writer.flush()
+                last_summary_time = now
+            else:
+                # no host synchronisation inside a step: the losses stay on the device until somebody looks at them
+                history.append(self.net.train_step_async(self.sess, blobs, self.state))
             if verbose and it % cfg.TRAIN.DISPLAY == 0:
                 rpn_loss_cls, rpn_loss_box, loss_cls, loss_box, total_loss = history[-1].cpu().tolist()
                 print('iter: %d / %d, total loss: %.6f\n >>> rpn_loss_cls: %.6f\n >>> rpn_loss_box: %.6f\n >>> loss_cls: %.6f\n'
@@ -199,13 +231,15 @@ def filter_roidb(roidb):
 
 
 def train_net(network, sess, data_layer, max_iters=40000, all_reduce=None, world_size=1, pretrained_model=None, output_dir=None,
-              resume=None, write_snapshots=True):
+              resume=None, write_snapshots=True, tb_dir=None, data_layer_val=None):
     """Train a Faster R-CNN network (reference signature minus imdb/roidb): pretrained_model = ImageNet checkpoint prefix
     (train_val.py:177-202), output_dir = where snapshots go every cfg.TRAIN.SNAPSHOT_ITERS, resume = (ckpt, pkl).
-    Data-parallel runs pass the SAME output_dir to every rank (all replicas must resume from the same snapshot: weights,
+    tb_dir = directory of the TensorBoard event file (None: no summaries), data_layer_val = the validation minibatch iterator whose
+    summaries go to `<tb_dir>_val`.  Data-parallel runs pass the SAME output_dir to every rank (all replicas must resume from the same snapshot: weights,
     Momentum slots, iteration and sampling seed -- otherwise they diverge and issue different numbers of all-reduces) and
     write_snapshots = (rank == 0)."""
-    sw = SolverWrapper(sess, network, data_layer, all_reduce=all_reduce, world_size=world_size, write_snapshots=write_snapshots)
+    sw = SolverWrapper(sess, network, data_layer, all_reduce=all_reduce, world_size=world_size, write_snapshots=write_snapshots,
+                       tb_dir=tb_dir, data_layer_val=data_layer_val)
     start = 0
     if resume is None and output_dir is not None and os.path.isdir(output_dir):
         lsf, nfiles, sfiles = find_previous(output_dir)            # train_val.py:243-252: continue from the newest snapshot
@@ -218,6 +252,7 @@ def train_net(network, sess, data_layer, max_iters=40000, all_reduce=None, world
         sw.initialize(pretrained_model)
     print('Solving...')
     hist = sw.train_model(max_iters, start_iter=start, snapshot_dir=output_dir)
+    sw.close_writers()
     if output_dir is not None and write_snapshots and max_iters % cfg.TRAIN.SNAPSHOT_ITERS:
         sw.snapshot(max_iters, output_dir)                        # the reference snapshots the last iteration too (:338-340)
     if world_size > 1 and output_dir is not None:

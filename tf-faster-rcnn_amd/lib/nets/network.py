@@ -41,7 +41,7 @@ class Network(object):
         self._sample_seed = 0
         self.replay_stats = dict(eager=0, recorded=0, replayed=0)      # train_step_async under cfg.HIP.TRAIN_REPLAY
         self._replay_clock, self._train_arena, self._train_scope_key = 0, None, None     # LRU clock of the recordings, replay.Arena, the step's shape scope
-        self._train_state = None
+        self._train_state = None               # the solver handle of the last train_step_with_summary (get_summary's regulariser term)
         self._plan_batch = 0                   # images per launch that TEST-mode launch-size rules see (_plan_context); 0: as built
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
         self._h2_of = {}                       # activation address -> ops.H2 operand planes of that tensor (cfg.HIP.MFMA_H2)
@@ -583,6 +583,7 @@ class Network(object):
     def _build_network_impl(self, is_training=True):
         self._tape = []
         self._requires_grad = set()
+        self._act_summaries = []                        # this build's [head, rpn] (the backbones and _region_proposal append)
         self._h2_of, self._f32_missing = {}, set()      # planes are facts about THIS build's launches (buffers are reused across builds)
         net_conv = self._image_to_head(is_training)
         self._anchor_component()
@@ -898,6 +899,7 @@ class Network(object):
             rec.replay(dict(seed=self._sample_seed, gt=int(self._gt_boxes.shape[0])))
             sess.prepared.refreshed()                         # (the replayed refresh re-recorded the tier events: every reader waits again)
             self._predictions, self._losses, self._proposal_targets, self._anchor_targets = ent["views"]
+            self._act_summaries = ent["acts"]
             self._sample_seed += 2
             self.replay_stats["replayed"] += 1
             if pk is not None and not pk.done:
@@ -930,6 +932,7 @@ class Network(object):
             ent["rec"] = rec
             ent["gen"] = gen_before
             ent["views"] = (dict(self._predictions), dict(self._losses), dict(self._proposal_targets), dict(self._anchor_targets))
+            ent["acts"] = list(self._act_summaries)
             self.replay_stats["recorded"] += 1
         else:
             self.replay_stats["eager"] += 1
@@ -944,6 +947,7 @@ class Network(object):
             sess.picking = False
         ent["rec"] = None
         ent.pop("views", None)
+        ent.pop("acts", None)
         ent.pop("gen", None)
 
     @classmethod
@@ -965,6 +969,96 @@ class Network(object):
 
     def train_step_no_return(self, sess, blobs, train_op):
         self.train_step(sess, blobs, train_op)
+
+    # ------------------------------------------------------------------ TensorBoard summaries (network.py:47-66,437-450,481-511)
+    LOSS_TAGS = ("rpn_cross_entropy", "rpn_loss_box", "cross_entropy", "loss_box", "total_loss")     # self._losses keys = the scalar tags (:310-319,440-441)
+
+    def _summary_tensors(self, train_op):
+        """[(tag, kind, device tensor)] of one summary step, over the step's RETAINED device tensors: kind 'act' = the activation list
+        (histogram + zero_fraction, :57-60), 'score' = every prediction and target (:62-63,181,206,260), 'train' = every trainable
+        variable (:65-66; the solver's master copies, i.e. the values AFTER the step's update -- the reference leaves the order of the
+        summary and the update inside its one sess.run undefined).  The middle of a tag is the tensor's name here (there are no TF op
+        names): ACT/<scope>/<head|rpn_conv/3x3>/activations, SCORE/<key>/scores, TRAIN/<variable name>."""
+        out = []
+        for name, t in zip(("head", "rpn_conv/3x3"), self._act_summaries):
+            out.append(("ACT/%s/%s" % (self._scope, name), "act", t))
+        score = collections.OrderedDict()
+        for d in (self._anchor_targets, self._proposal_targets, self._predictions):      # (later dicts win a shared key like the reference's update())
+            for k, t in d.items():
+                if torch.is_tensor(t) and t.dtype == torch.float32:                    # (`counts` of the sampler is bookkeeping, not a target)
+                    score[k] = t
+        for k, t in score.items():
+            out.append(("SCORE/%s/scores" % k, "score", t))
+        if train_op is not None:
+            for p in train_op.params.values():
+                if p.dw:
+                    out.append(("TRAIN/%s/depthwise_weights" % p.scope, "train", p.w))
+                    continue
+                out.append(("TRAIN/%s/weights" % p.scope, "train", p.w))
+                if p.bias is not None:
+                    out.append(("TRAIN/%s/biases" % p.scope, "train", p.bias))
+        return out
+
+    def _gt_image_summary(self):
+        """network.py:40-55: the staged image + PIXEL_MEANS, BGR -> RGB, back at its original size, gt boxes drawn (host, PIL)."""
+        from frcnn_hip import summary
+        from utils.visualization import draw_bounding_boxes, resize_bilinear
+        bgr = self._image[0, :, :, :3].cpu().numpy().astype(np.float64) + np.asarray(cfg.PIXEL_MEANS, dtype=np.float64).reshape(1, 1, 3)
+        h, w, scale = self._im_info
+        rgb = resize_bilinear(bgr[:, :, ::-1], int(h / scale), int(w / scale))
+        pic = draw_bounding_boxes(rgb, self._gt_boxes.cpu().numpy(), self._im_info)
+        return summary.image("GROUND_TRUTH", pic[0].astype(np.uint8))
+
+    def _build_summary(self, train_op, loss_values, full):
+        """The serialised Summary of the step whose tensors this network holds right now: launches on the current stream (after the step),
+        one read-back.  full = False: the validation summary (image + losses, :437-441,450)."""
+        from frcnn_hip import summary
+        parts = [self._gt_image_summary()]
+        parts += [summary.scalar(k, v) for k, v in zip(self.LOSS_TAGS, loss_values)]
+        if full:
+            items = self._summary_tensors(train_op)
+            stats = ops.summary_stats([t if t.is_contiguous() else t.contiguous() for _, _, t in items])
+            limits = ops.summary_limits()
+            for (tag, kind, _), st in zip(items, stats):
+                if kind == "act":
+                    parts.append(summary.histogram(tag + "/activations", st, limits))
+                    parts.append(summary.scalar(tag + "/zero_fraction", summary.zero_fraction(st)))
+                else:
+                    parts.append(summary.histogram(tag, st, limits))
+        return b"".join(parts)
+
+    def train_step_with_summary(self, sess, blobs, train_op):
+        """network.py:500-511: train_step plus the serialised Summary (bytes for summary.FileWriter.add_summary).  The step itself is
+        train_step_async -- replayed when its shape has a recording, recorded or eager otherwise, exactly as without a summary -- and the
+        statistics kernel runs after it on the same stream over the tensors the step left behind; nothing it writes is read by a later
+        step."""
+        self._train_state = train_op
+        losses = self.train_step_async(sess, blobs, train_op)
+        vals = tuple(float(v) for v in losses.cpu().tolist())
+        return vals + (self._build_summary(train_op, vals, True),)
+
+    def get_summary(self, sess, blobs, train_op=None):
+        """network.py:481-486: the validation summary -- TRAIN-mode forward + losses on `blobs`, eagerly, NO update: weights, momentum and
+        the gradient buffer are not touched, and the sampling seed is restored, so the training run continues bit for bit as if this had
+        not run (the forward pass overwrites only activations and targets, which every step rewrites before reading).  total_loss carries
+        the regulariser's value when a solver handle is known (the argument, or the last train_step_with_summary's)."""
+        assert self._mode == "TRAIN"
+        train_op = self._train_state if train_op is None else train_op
+        seed = self._sample_seed
+        with self._train_scope(sess, blobs):
+            try:
+                self._stage_train_inputs(sess, blobs)
+                losses = self._train_forward_staged(sess)
+            finally:
+                self._sample_seed = seed
+            parts = [losses[k].view(1) for k in ("rpn_cross_entropy", "rpn_loss_box", "cross_entropy", "loss_box")]
+            total = parts[0] + parts[1] + parts[2] + parts[3]
+            if train_op is not None and train_op.params:
+                reg = torch.zeros((1,), dtype=torch.float32, device=sess.device)
+                train_op.regularization_loss(reg)
+                total = total + reg
+            vals = tuple(float(v) for v in torch.cat(parts + [total]).cpu().tolist())
+            return self._build_summary(None, vals, False)
 
     def detect_device(self, sess, image_d, im_info, im_shape, max_per_image=100, thresh=0.0, out=None, count=None):
         """image(s) already in HBM -> final detections in HBM: forward + the whole of lib/model/test.py:95-102,

@@ -4,6 +4,8 @@ algorithmic GB/s, bit equality against cfg 9.  Round 5.
 
     python scratch/h2_conv3.py 9,21,12[,more] [shape,shape,...] [--lib path/to/ablation.so] [--single N]
 
+A negative id is a by-shape rule of run_h2 (csrc/gemm_h2.hip): -1 the shipped one, -9 the one before the ping-pong shape classes.
+
 --single N: only N launches of the first cfg on the first shape (for rocprofv3 --pmc passes: one kernel, nothing else).
 """
 import os, sys
@@ -27,6 +29,7 @@ shapes = {  # name: (G, M, N, K, residual, f32 out, planes out, mean rows)
     "b4c3x8pm": (8, 14700, 2048, 512, "planes", False, False, 49),  # ... as shipped: the residual arrives as unit 2's operand planes
     "b3c3x8":  (1, 19152, 1024, 256, True, True, True, 0),         # block3 conv3 (23 per step)
     "b2c3x8":  (1, 75000, 512, 128, True, True, True, 0),          # block2 conv3
+    "b4c3x8r": (1, 117600, 2048, 512, True, False, True, 0),       # block4 unit 1 conv3 as shipped: float32 residual (the crop), planes only out
     "b4c3x8p": (1, 117600, 2048, 512, "planes", False, True, 0),   # ... as shipped since round 5 (cfg.HIP.H2_TRUNK_PLANES): residual read as planes, planes only out
     "b3c3x8p": (1, 19152, 1024, 256, "planes", False, True, 0),
     "b3scx8":  (1, 19152, 1024, 512, False, True, True, 0),        # block3 unit 1 shortcut

@@ -766,32 +766,41 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     }
   };
 
-  // the standalone epilogue of the tile under the c_* cursor: every part back to back, after the tile's last fold
-  auto epilogue = [&]() {
+  // the standalone epilogue of the tile under the c_* cursor: every part back to back, after the tile's last fold.  live == false (the
+  // ping-pong schedule only: a wave whose rows all lie past M): the wave has no results -- it executes the barriers and nothing else
+  auto epilogue = [&](bool live) {
     const TileRef T{c_bm0, c_bn0, c_g, c_cpar};
-    ep_scale_act(T);
-    ep_mask(T);
+    if (live) {
+      ep_scale_act(T);
+      ep_mask(T);
+    }
     if (p.mean_part) {
+      if (live) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i) ep_mean(T, i);
+        for (int i = 0; i < TM; ++i) ep_mean(T, i);
+      }
       c_cpar ^= 1;
       return;
     }
+    if (live) {
 #pragma unroll
-    for (int i = 0; i < TM; ++i) ep_store_f32(T, i);
+      for (int i = 0; i < TM; ++i) ep_store_f32(T, i);
+    }
     if (p.yp) {
       float mx[TM];
-      ep_rowmax_write(mx);
+      if (live) ep_rowmax_write(mx);
       if (BN / WN > 1) {
         // raw barrier + lgkmcnt(0): the exchange goes through LDS only.  __syncthreads() would add vmcnt(0), i.e. wait until the float32
         // stores just issued (and the slabs in flight) have COMPLETED -- 7-9 thousand cycles per drain under a write burst
         // (profiles/r04_w_h2_tile_boundary.txt)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        ep_rowmax_merge(mx);
+        if (live) ep_rowmax_merge(mx);
       }
+      if (live) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i) ep_store_planes(T, i, mx[i]);
+        for (int i = 0; i < TM; ++i) ep_store_planes(T, i, mx[i]);
+      }
       if (BN / WN > 1) {                                                         // red[] is reused by the next tile
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -982,22 +991,32 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
           for (int r = 0; r < 16; ++r) tot[i][j][r] = __builtin_fmaf(tmp[i][j][r], ainv[i], tot[i][j][r]);
     };
     // returns whether slab q + 2 was issued (the group-0 wait at the end of MFMA(q) needs to know)
-    auto pp_mem = [&](auto pos_c, bool fold_prev) -> bool {
+    auto pp_mem = [&](auto pos_c, bool fold_prev, bool live) -> bool {
       constexpr int POS = decltype(pos_c)::value;
       const char* sb = smem + cur * STAGE;
+      if (live) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const char* q = sb + w_row + j * 32 * 64 + (((2 * t + khalf) ^ sw) * 16);
-          fwh[t][j] = __builtin_bit_cast(h8, *(const uint4*)(q));
-          fwl[t][j] = __builtin_bit_cast(h8, *(const uint4*)(q + WP));
+          for (int j = 0; j < TN; ++j) {
+            const char* q = sb + w_row + j * 32 * 64 + (((2 * t + khalf) ^ sw) * 16);
+            fwh[t][j] = __builtin_bit_cast(h8, *(const uint4*)(q));
+            fwl[t][j] = __builtin_bit_cast(h8, *(const uint4*)(q + WP));
+          }
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            const char* q = sb + x_row + i * 32 * 64 + (((2 * t + khalf) ^ sw) * 16);
+            fxh[t][i] = __builtin_bit_cast(h8, *(const uint4*)(q));
+            fxl[t][i] = __builtin_bit_cast(h8, *(const uint4*)(q + XP));
+          }
         }
+      } else {            // (no instruction: the fragments of the last live slab end here, not at the next live tile's MFMAs)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const char* q = sb + x_row + i * 32 * 64 + (((2 * t + khalf) ^ sw) * 16);
-          fxh[t][i] = __builtin_bit_cast(h8, *(const uint4*)(q));
-          fxl[t][i] = __builtin_bit_cast(h8, *(const uint4*)(q + XP));
+        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j) asm volatile("" : "=v"(fwh[t][j]), "=v"(fwl[t][j]));
+#pragma unroll
+          for (int i = 0; i < TM; ++i) asm volatile("" : "=v"(fxh[t][i]), "=v"(fxl[t][i]));
         }
       }
       const bool more = left > 0;
@@ -1015,32 +1034,34 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
       seg_barrier();
       return more;
     };
-    auto pp_mfma = [&](auto pos_c, bool issued) {
+    auto pp_mfma = [&](auto pos_c, bool issued, bool live) {
       constexpr int POS = decltype(pos_c)::value;
       __builtin_amdgcn_s_setprio(1);
+      if (live) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+          for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            if (POS == 0 && t == 0) {
-              f32x16 z;
+            for (int j = 0; j < TN; ++j) {
+              if (POS == 0 && t == 0) {
+                f32x16 z;
 #pragma unroll
-              for (int r = 0; r < 16; ++r) z[r] = 0.f;
-              tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxh[t][i], z, 0, 0, 0);
-            } else {
-              tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxh[t][i], tmp[i][j], 0, 0, 0);
+                for (int r = 0; r < 16; ++r) z[r] = 0.f;
+                tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxh[t][i], z, 0, 0, 0);
+              } else {
+                tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxh[t][i], tmp[i][j], 0, 0, 0);
+              }
             }
-          }
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+          for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwl[t][j], fxh[t][i], tmp[i][j], 0, 0, 0);
+            for (int j = 0; j < TN; ++j) tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwl[t][j], fxh[t][i], tmp[i][j], 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+          for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxl[t][i], tmp[i][j], 0, 0, 0);
+            for (int j = 0; j < TN; ++j) tmp[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[t][j], fxl[t][i], tmp[i][j], 0, 0, 0);
+        }
       }
       __builtin_amdgcn_s_setprio(0);
       if (grp == 0) {
@@ -1066,16 +1087,30 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
     if (grp == 1) seg_barrier();                                // one segment behind from here on
     const int nkb = p.nsteps >> 2;
     for (int tl = 0; tl < my_tiles; ++tl) {
-      init_tot();
+      // A wave whose 64 rows all lie past M (the last row tile of a batch entry: with rows 128 .. 255 past M that is all of group 1) has
+      // nothing to multiply: for this tile it reads no fragments, issues no MFMAs, forms no start value, folds nothing and stores
+      // nothing.  Wave-uniform, per tile.  It still issues its share of every slab (the ring and the counted waits do not know about
+      // tiles; the rows it fetches past M are set_tile's re-reads of row M - 1) and executes every barrier of the segments and of the
+      // epilogue, so the one-segment offset between the groups holds.  The skipped branches DEFINE what they would have written
+      // (empty asm, no instruction): otherwise the fragments and accumulators of the previous tile stay live through them and the
+      // kernel spills.
+      const bool live = __builtin_amdgcn_readfirstlane(c_bm0 + wm0 < p.M ? 1 : 0) != 0;
+      if (live) init_tot();
+      else {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) asm volatile("" : "=v"(tot[i][j]));
+      }
       for (int kb = 0; kb < nkb; ++kb) {
         bool is;
-        is = pp_mem(std::integral_constant<int, 0>{}, kb > 0); pp_mfma(std::integral_constant<int, 0>{}, is);
-        is = pp_mem(std::integral_constant<int, 1>{}, false);  pp_mfma(std::integral_constant<int, 1>{}, is);
-        is = pp_mem(std::integral_constant<int, 2>{}, false);  pp_mfma(std::integral_constant<int, 2>{}, is);
-        is = pp_mem(std::integral_constant<int, 3>{}, false);  pp_mfma(std::integral_constant<int, 3>{}, is);
+        is = pp_mem(std::integral_constant<int, 0>{}, live && kb > 0, live); pp_mfma(std::integral_constant<int, 0>{}, is, live);
+        is = pp_mem(std::integral_constant<int, 1>{}, false, live);          pp_mfma(std::integral_constant<int, 1>{}, is, live);
+        is = pp_mem(std::integral_constant<int, 2>{}, false, live);          pp_mfma(std::integral_constant<int, 2>{}, is, live);
+        is = pp_mem(std::integral_constant<int, 3>{}, false, live);          pp_mfma(std::integral_constant<int, 3>{}, is, live);
       }
-      fold();
-      epilogue();
+      if (live) fold(); else c_par ^= nkb & 1;                    // (the block-scale parity follows the stream, folded or not)
+      epilogue(live);
       c_tile += W8;
       if (tl + 1 < my_tiles) set_ctile(c_tile);
     }
@@ -1116,7 +1151,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
         continue;
       }
     }
-    epilogue();
+    epilogue(true);
     c_tile += W8;
     if (tl + 1 < my_tiles) set_ctile(c_tile);
   }
@@ -1259,6 +1294,9 @@ static int h2_dispatch(const GemmH2Params& p, int cfg, hipStream_t st) {
 }
 
 static int run_h2(GemmH2Params& p, int cfg, hipStream_t st);
+#ifndef FRCNN_H2_PP_CLASSES
+#define FRCNN_H2_PP_CLASSES 7           // run_h2's shape classes as a mask (measurement builds take one at a time into the three-chain
+#endif                                  // pipeline, scratch/ablation_lib.py): 1 products, 2 float32-residual conv3, 4 planes-residual conv3
 
 // the fields the three entry points share; each entry then sets its own form (mask / mean_part, mean_rows, wshare)
 static GemmH2Params h2_params(const void* x_planes_d, const float* x_inv_d, const void* w_planes_d, const float* w_inv_d, const float* bias_d,
@@ -1277,7 +1315,8 @@ static GemmH2Params h2_params(const void* x_planes_d, const float* x_inv_d, cons
 // output); W: frcnn_h2_pack_w(W [G][N][K]); res / y [G*M][N] f32 (y may be null when only planes are wanted); the residual may be
 // given as operand planes instead (res_planes [2][G*M][N] + res_inv [N/128][G*M], e.g. an earlier launch's `yp`);
 // yp / y_inv: planes [2][G*M][N] + [N/128][G*M] of the result for the next GEMM (null: not emitted).
-// cfg: -1 by shape, else a tile configuration id (A/B runs; per call, no process-wide state).
+// cfg: -1 by shape (negative codes: earlier rules for A/B runs, run_h2), else a tile configuration id (A/B runs; per call, no
+// process-wide state).
 extern "C" int frcnn_gemm_h2(const void* x_planes_d, const float* x_inv_d, const void* w_planes_d, const float* w_inv_d, const float* bias_d,
                              const float* res_d, const void* res_planes_d, const float* res_inv_d, float* y_d, void* y_planes_d, float* y_inv_d,
                              int G, int M, int N, int K, int act, int cfg, void* stream) {
@@ -1314,10 +1353,14 @@ static int run_h2(GemmH2Params& p, int cfg, hipStream_t st) {
   const int G = p.batch, M = p.M, N = p.N, K = p.K;
   if (cfg < 0) {
     // By shape.  Every configuration multiplies and folds in the same order (bit-identical results), so this is a speed choice only.
+    // cfg == -9: the rule as it stood before the shape classes below (A/B runs from one build); it is -1 without them.
+    const bool classes = cfg == -1;
+    if (cfg == -9) cfg = -1;
     // The ping-pong schedule (cfg 21) keeps the matrix pipe busier per joule (profiles/r04_e_h2_power.txt: every configuration sits at
-    // the 1 400 W socket limit, so time follows energy) but owns a whole CU per 256 x 128 tile: it pays on long-K launches whose tile
-    // epilogues are a small part (K >= 1024: 64 slabs per tile), with at least one tile per CU and 256-row tiles that waste < 4 % of M.
-    const long long mt256 = (M + 255) / 256;
+    // the 1 400 W socket limit, so time follows energy) and carries 25 % fewer operand bytes per MFMA, but owns a whole CU per 256 x 128
+    // tile.  The general rule: long-K launches whose tile epilogues are a small part (K >= 1024: 64 slabs per tile), with at least one
+    // tile per CU and 256-row tiles that waste < 4 % of M.
+    const long long mt256 = (M + 255) / 256, t256 = mt256 * (N / 128) * G;
 #ifndef FRCNN_H2_PP_MIN_K
 #define FRCNN_H2_PP_MIN_K 1024          // (scratch/bench_ablation.py rebuilds with other values: 512 measured in the pipeline, profiles/r04_u)
 #endif
@@ -1325,8 +1368,32 @@ static int run_h2(GemmH2Params& p, int cfg, hipStream_t st) {
     // result tensor written: not the fused-mean form, which loses on one workgroup per CU -- profiles/r05_b) on the ping-pong schedule too
     // -6: cfg 34 for the conv3 class only, the long-K launches stay on cfg 21
     const int pp_min_k = ((cfg == -4 || cfg == -5 || cfg == -6) && !p.mean_part) ? 512 : FRCNN_H2_PP_MIN_K;
-    const int pp_cfg = (cfg == -3 || cfg == -4 || (cfg == -6 && K < FRCNN_H2_PP_MIN_K)) ? 34 : 21;
-    const bool pp = K >= pp_min_k && mt256 * 256 * 100 <= (long long)M * 104 && mt256 * (N / 128) * G >= 256;
+    int pp_cfg = (cfg == -3 || cfg == -4 || (cfg == -6 && K < FRCNN_H2_PP_MIN_K)) ? 34 : 21;
+    const bool waste256_ok = mt256 * 256 * 100 <= (long long)M * 104;
+    bool pp = K >= pp_min_k && waste256_ok && t256 >= 256;
+    // Shape classes with a measurement of their own (profiles/h2_pingpong_shapes.txt: isolated 8-image launches under cfg -9 -> -1, and
+    // each class alone in the three-chain pipeline against cfg -9's 539.6 images/s).  A wave whose 64 rows lie past M no longer multiplies (k_gemm_h2, the
+    // ping-pong tile loop), so for these the M waste counts in 64-row wave blocks: M = 2400 wastes 1.3 %, not 6.7 %.
+    bool to31 = false;
+    if (classes && !p.mean_part && !p.mask) {
+      const long long m64 = (M + 63) / 64 * 64;
+      const bool waste64_ok = m64 * 100 <= (long long)M * 104;
+      // batched float32-out products (the Winograd products of the tail's conv2, 121 x [2400 x 512] . [512 x 512]): 582 -> 565 us,
+      // 544.4 images/s
+      const bool products = (FRCNN_H2_PP_CLASSES & 1) && G > 1 && p.y && !p.yp && !p.res && !p.resp && K >= 512 && waste64_ok && t256 >= 256;
+      // conv3 with a float32 residual and planes out, K = 512 (block4 unit 1): 1 110 -> 1 100 us on cfg 21, -> 993 us with the 16-byte
+      // plane stores of cfg 34; 542.5 images/s
+      const bool conv3_f32res = (FRCNN_H2_PP_CLASSES & 2) && p.res && p.yp && K == 512 && waste64_ok && t256 >= 256;
+      // (not a class: long K with 128 .. 255 tiles of 256 x 128 -- block3 conv1, 19 152 x 1024 -> 256, 150 tiles.  50.1 -> 44.7 us
+      // isolated, but nothing in the three-chain pipeline, where a tile that owns a whole CU keeps the other chains' workgroups off
+      // it: 539.3 against 539.6 images/s.  It stays on cfg 31 under the one-tile-per-CU condition above.)
+      if (conv3_f32res && !pp) pp_cfg = 34;
+      pp = pp || products || conv3_f32res;
+      // planes residual, planes only out, K = 512 (block4 unit 2 conv3): the standalone light boundary with the raw planes residual beats
+      // the deferred epilogue, 1 155 -> 1 109 us (1 147 -> 1 101 us in profiles/h2_mean_valu.txt), 544.2 images/s; K <= 256 (block3's
+      // identity units) stays on cfg 40
+      to31 = (FRCNN_H2_PP_CLASSES & 4) && p.resp && p.yp && !p.y && K == 512;
+    }
     // fewer than 150 tiles of 128 x 128 (a single image's launches: batch-1 latency mode): 64-row tiles, three workgroups per CU
     // (profiles/r03_g_h2_sweep.txt: 21.8 vs 30.9 us on one image's block3 conv1); in the 4-image pipeline these lose (r03_l_ab.txt)
     const bool tiny = (long long)((M + 127) / 128) * (N / 128) * G < 150;
@@ -1340,7 +1407,7 @@ static int run_h2(GemmH2Params& p, int cfg, hipStream_t st) {
     // planes only out, the identity units of a trunk kept as planes: block3 conv3 65.6 -> 60.0 us, block4 conv3 1 190 -> 1 172 us -- and
     // costs 1-5 % where the standalone epilogue was short (float32 out without residual: its stores then sit in the next tile's slabs
     // instead of beside the co-resident workgroup's K loop); 64-row tiles (cfg 41) lose everywhere.  cfg == -8: DE wherever it exists.
-    const bool de = cfg != -2 && cfg != -7 && !p.mean_part && !p.mask && ((p.resp && p.yp && !p.y) || cfg == -8);
+    const bool de = cfg != -2 && cfg != -7 && !p.mean_part && !p.mask && ((p.resp && p.yp && !p.y) || cfg == -8) && !to31;
     cfg = pp ? pp_cfg : tiny ? (cfg == -2 ? 12 : (de && cfg == -8) ? 41 : 33) : (cfg == -2 ? 9 : de ? 40 : 31);
   }
   if (p.mean_part && (cfg == 40 || cfg == 41)) cfg = cfg == 40 ? 31 : 33;     // (the fused-mean form keeps the standalone epilogue: same tiles)

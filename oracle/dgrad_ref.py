@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- float64 statements of the data gradients of the reverse sweep (frcnn_hip/train.py _sweep) and the
-elementwise error bound the op-level tests hold them to.
+"""TEST INFRASTRUCTURE ONLY -- float64 statements of the data gradients of the reverse sweep (frcnn_hip/sweep.py: dgrad_route names
+them, DGRAD issues them) and the elementwise error bound the op-level tests hold them to.
 
 dX of y = conv2d(pad(x), W, stride) is a scatter of dY through the filter taps; dgrad64 states it tap by tap in float64 (any pad,
 negative ones included, so a shifted pad can be stated too).  The bound of a float32 result is elementwise and scaled to the magnitude

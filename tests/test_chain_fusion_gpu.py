@@ -1,4 +1,4 @@
-"""The training step's data-gradient chain with its elementwise passes folded into the launches around them (frcnn_hip/train.py _sweep:
+"""The training step's data-gradient chain with its elementwise passes folded into the launches around them (frcnn_hip/sweep.py Sweep:
 ReLU-gradient masks in the producing launch's epilogue, identity-shortcut gradients borrowed instead of copied, operand planes of dY out
 of the Winograd output transform; lib/nets/resnet_v1.py's bottleneck in reverse).  Every mask is an exact select, so the float32 results
 are BIT equal to the unfused sequence -- per C-ABI entry and over a whole training step.  Operand planes: the GEMM epilogue emits exactly

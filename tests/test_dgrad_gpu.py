@@ -1,5 +1,5 @@
-"""GPU: every data-gradient route of the reverse sweep (frcnn_hip/train.py _sweep) called through ops exactly as the sweep calls it --
-same filter preparation, pads, accumulate / residual handling, ReLU mask and operand planes -- against the float64 statement of the
+"""GPU: every data-gradient route of the reverse sweep, through the route function the sweep itself calls (frcnn_hip/sweep.py DGRAD: its
+filter preparation, pads, accumulate / residual handling, ReLU mask and operand planes) -- against the float64 statement of the
 same operation (oracle/dgrad_ref.py), plus the other kernels of the sweep: stride-2 depthwise dgrad at MobileNet's asymmetric SAME
 pads, relu_bwd / relu6_bwd at their edges, add_strided, spatial_mean_bwd and the heads' filter-gradient fallback.
 
@@ -50,68 +50,50 @@ def _same_planes(got, want):
         assert np.array_equal(g_, w_), name
 
 
+class Scratch(object):
+    """What the route functions are given in the session's place (frcnn_hip/sweep.py: buf / h2_buf / buf_pair): fresh device tensors, zeroed
+    where the route asks for zeros and filled with the sentinel where it does not, operand planes pre-filled 0x5a / -1.0, so that an
+    element a kernel should have written and did not is seen; `handed` keeps every buffer by the name it was asked for under."""
+
+    def __init__(self, dev):
+        self.dev, self.handed = dev, {}
+
+    def buf(self, name, shape, zero=False):
+        t = torch.zeros(tuple(shape), dtype=torch.float32, device=self.dev) if zero else torch.full(tuple(shape), SENT, dtype=torch.float32, device=self.dev)
+        self.handed[name] = t
+        return t
+
+    def h2_buf(self, name, rows, K):
+        from frcnn_hip import ops
+        p = self.handed[name] = ops.H2.empty(rows, K, self.dev)
+        p.planes.fill_(0x5a), p.inv.fill_(-1.0)
+        return p
+
+    def buf_pair(self, name, N, K):
+        from frcnn_hip import ops
+        return (torch.empty(int(ops.lib().frcnn_h2_planes_bytes(int(N), int(K))), dtype=torch.uint8, device=self.dev),
+                torch.empty((1, int(N)), dtype=torch.float32, device=self.dev))
+
+
+def prepared(key, fn):
+    return fn()
+
+
 def run_route(route, case, gy, wf, x, res, dev, mask=True):
-    """One data gradient through ops as _sweep issues it.  had = res is not None (accumulate into a buffer that holds res).
+    """One data gradient through the route function the sweep calls (frcnn_hip/sweep.py DGRAD[route]), asked to emit operand planes wherever
+    the route can.  had = res is not None (accumulate into a buffer that holds res).
     Returns (dX float32 [N,H,W,Cin] on the host, operand planes or None, what the mask was (None when the route took none))."""
-    from frcnn_hip import ops
+    from frcnn_hip import ops, sweep
     _, N, H, W, Cin, Cout, k, stride, pad = case
     OH, OW = gy.shape[1], gy.shape[2]
-    M = N * OH * OW
-    had = res is not None
-    gyd, wfd, xd = T(gy, dev), T(wf, dev), T(x, dev)
     shape = (N, H, W, Cin)
     guard, gx = _guarded(shape, dev, None if res is None else T(res, dev))
-    mk = xd if mask else None
-    planes = None
-    if route == "winograd":
-        m = 7 if (OH == 7 and OW == 7) else 4
-        G, Tl = ops.winograd_points(m), ops.winograd_tiles(N, OH, OW, m)
-        u = ops.winograd_filter_transform_device(wfd, m, True)
-        fused = mk is not None and not had
-        if fused and Cin % 128 == 0:
-            planes = ops.H2.empty(N * H * W, Cin, dev)
-            planes.planes.fill_(0x5a), planes.inv.fill_(-1.0)
-        dst = torch.full(shape, SENT, dtype=torch.float32, device=dev) if had else gx
-        ops.conv3x3_winograd(gyd, u, None, 0, out=dst, v_buf=torch.empty((G, Tl, Cout), device=dev),
-                             m_buf=torch.empty((G, Tl, Cin), device=dev), mask=mk if fused else None, out_planes=planes)
-        if had:
-            ops.add_strided(dst, gx, 1, True)
-        mk = mk if fused else None
-    elif route == "flipped":
-        wd = ops.flip_transpose_filter(wfd)
-        dpad = (k - 1 - pad[0], k - 1 - pad[1], k - 1 - pad[2], k - 1 - pad[3])
-        ops.conv2d(gyd, wd, None, k, k, 1, dpad, 0, gx if had else None, 1, out=gx, mask=mk)
-    elif route == "h2":
-        wd = ops.flip_transpose_filter(wfd)
-        gp = ops.h2_split(gyd.view(M, Cout))
-        wq = ops.h2_pack_w(wd.view(Cin, Cout))
-        if mk is not None:
-            planes = ops.H2.empty(M, Cin, dev)
-            planes.planes.fill_(0x5a), planes.inv.fill_(-1.0)
-        ops.gemm_h2(gp, wq, 1, M, Cin, Cout, None, gx.view(M, Cin) if had else None, 0, out=gx.view(M, Cin),
-                    mask=None if mk is None else mk.view(M, Cin), out_planes=planes)
-    elif route == "padded":
-        Cp = (Cout + 31) // 32 * 32
-        wdp = ops.transpose_pad(wfd.view(Cout, Cin), Cp)
-        gyp = torch.zeros((N, OH, OW, Cp), dtype=torch.float32, device=dev)
-        ops.t_copy(gyp[..., :Cout], gyd)
-        ops.conv2d(gyp, wdp.view(Cin, 1, 1, Cp), None, 1, 1, 1, (0, 0, 0, 0), 0, gx if had else None, 1, out=gx, mask=mk)
-    elif route == "upsampled":
-        up_h, up_w = (OH - 1) * stride + 1, (OW - 1) * stride + 1
-        up_pad = (k - 1 - pad[0], H - up_h - (k - 1 - pad[0]) + k - 1, k - 1 - pad[2], W - up_w - (k - 1 - pad[2]) + k - 1)
-        assert min(up_pad) >= 0
-        wd = ops.flip_transpose_filter(wfd)
-        up = torch.zeros((N, up_h, up_w, Cout), dtype=torch.float32, device=dev)
-        ops.add_strided(gyd, up, stride, False)
-        ops.conv2d(up, wd, None, k, k, 1, up_pad, 0, gx if had else None, 1, out=gx, mask=mk)
-    elif route == "gather":
-        ops.conv2d_dgrad_strided(gyd, wfd, stride, pad, H, W, gx, had)
-        mk = None
-    else:
-        raise ValueError(route)
+    m = (7 if (OH == 7 and OW == 7) else 4) if route == "winograd" else None
+    masked, planes, _, _ = sweep.DGRAD[route](ops, Scratch(dev), prepared, case[0], T(gy, dev), T(wf, dev), k, stride, pad, gx, None if res is None else gx,
+                                              T(x, dev) if mask else None, emit=True, m=m)
     torch.cuda.synchronize()
     assert _tail_ok(guard, shape), "%s wrote past the end of dX" % route
-    return gx.cpu().numpy(), planes, (None if mk is None else x)
+    return gx.cpu().numpy(), planes, (x if masked else None)
 
 
 def _wino_out_groups(m, N, H, W):
@@ -177,10 +159,10 @@ def test_dgrad_route_vs_float64(dev, rc, had, kind):
     ("roi37_m7", 37, 7, 7, 256, 256, 512),
 ], ids=lambda c: c[0])
 def test_h2_dgrad_on_winograd_emitted_planes_vs_float64(dev, case, kind):
-    """The bottleneck in reverse as _sweep runs it: conv2's Winograd data gradient (masked, fresh) emits its result as operand planes with
+    """The bottleneck in reverse as the sweep runs it: conv2's Winograd data gradient (masked, fresh) emits its result as operand planes with
     row-group scales (emitted[key]), and conv1's h2 data gradient reads them as its dY instead of an h2_split.  Against float64 of conv1's
     data gradient of conv2's float32 result: the route's elementwise bound and the f32 class of the flipped-direct kernel on the same dY."""
-    from frcnn_hip import ops
+    from frcnn_hip import ops, sweep
     _, N, H, W, C2in, C2out, C1in = case
     M = N * H * W
     case2 = (case[0], N, H, W, C2in, C2out, 3, 1, R.SAME3)
@@ -189,10 +171,8 @@ def test_h2_dgrad_on_winograd_emitted_planes_vs_float64(dev, case, kind):
     assert planes is not None
     case1 = (case[0], N, H, W, C1in, C2in, 1, 1, R.ZERO)
     _, wf1, x1, _ = R.operands(kind, N, H, W, C1in, C2in, 1, 1, R.ZERO, seed=M + C1in + 1)
-    wq = ops.h2_pack_w(ops.flip_transpose_filter(T(wf1, dev)).view(C1in, C2in))
     guard, gx = _guarded((N, H, W, C1in), dev)
-    x1d = T(x1, dev)
-    ops.gemm_h2(planes, wq, 1, M, C1in, C2in, None, None, 0, out=gx.view(M, C1in), mask=x1d.view(M, C1in))
+    sweep.dgrad_h2(ops, Scratch(dev), prepared, case[0], T(dy1, dev), T(wf1, dev), 1, 1, R.ZERO, gx, None, T(x1, dev), gy_planes=planes)
     torch.cuda.synchronize()
     assert _tail_ok(guard, (N, H, W, C1in))
     got = gx.cpu().numpy()
@@ -304,30 +284,24 @@ def test_spatial_mean_bwd_hw49(dev, R_):
     ("k3s2_M12544", 1, 223, 225, 12, 32, 3, 2, (1, 1, 1, 1)),             # M = 112 x 113 = 12656
 ])
 def test_head_filter_gradient_fallback_vs_float64(dev, case):
-    """_sweep's wgrad() when conv2d_wgrad_supported is false (or ts.wgrad_tn = False): transpose_pad of dY, transpose_pad / im2col_t of X,
-    the forward MFMA kernel on the padded pair, colsum for the bias"""
-    from frcnn_hip import ops
+    """The sweep's filter gradient (frcnn_hip/sweep.py filter_gradient) when conv2d_wgrad_supported is false or TrainState.wgrad_tn is off:
+    transpose_pad of dY, transpose_pad / im2col_t of X, the forward MFMA kernel on the padded pair, colsum for the bias"""
+    import types
+    from frcnn_hip import ops, sweep
     _, N, H, W, Cin, Cout, k, stride, pad = case
     OH, OW = R.conv_out(H, k, stride, pad[0], pad[1]), R.conv_out(W, k, stride, pad[2], pad[3])
     M = N * OH * OW
-    Mp = (M + 31) // 32 * 32
+    KK = k * k * Cin
     rng = np.random.RandomState(M + Cin)
     x = np.maximum(rng.randn(N, H, W, Cin), 0).astype(np.float32)
     gy = (rng.randn(N, OH, OW, Cout) * (rng.rand(N, OH, OW, Cout) < 0.5)).astype(np.float32)
-    xd, gyd = T(x, dev), T(gy, dev)
-    gyT = torch.full((Cout, Mp), SENT, dtype=torch.float32, device=dev)
-    ops.transpose_pad(gyd.view(M, Cout), Mp, out=gyT)
-    KK = k * k * Cin
-    xT = torch.full((KK, Mp), SENT, dtype=torch.float32, device=dev)
-    if k == 1 and stride == 1:
-        ops.transpose_pad(xd.view(M, Cin), Mp, out=xT)
-    else:
-        ops.im2col_t(xd, k, k, stride, pad, OH, OW, Mp, out=xT)
-    assert bool((gyT[:, M:] == 0).all()) and bool((xT[:, M:] == 0).all()), "the pad columns must be zero"
     guard, gw = _guarded((Cout, KK), dev)
-    ops.conv2d(gyT.view(1, 1, Cout, Mp), xT.view(KK, 1, 1, Mp), None, 1, 1, out=gw.view(1, 1, Cout, KK))
     gb_guard, gb = _guarded((Cout,), dev)
-    ops.colsum(gyd.view(M, Cout), gb)
+    scratch = Scratch(dev)
+    sweep.filter_gradient(ops, scratch, "", T(gy, dev), T(x, dev), k, stride, pad, types.SimpleNamespace(grad_w=gw, K=KK, bias=gb, grad_b=gb), False, False)
+    gyT, xT = scratch.handed["bwd/gyT"], scratch.handed["bwd/xT"]
+    assert gyT.shape[1] == xT.shape[1] == (M + 31) // 32 * 32 and xT.shape[0] == KK
+    assert bool((gyT[:, M:] == 0).all()) and bool((xT[:, M:] == 0).all()), "the pad columns must be zero"
     torch.cuda.synchronize()
     assert _tail_ok(guard, (Cout, KK)) and _tail_ok(gb_guard, (Cout,))
     want = R.wgrad64(gy, x, k, k, stride, pad).reshape(Cout, KK)

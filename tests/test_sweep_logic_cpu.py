@@ -1,4 +1,4 @@
-"""CPU: the bookkeeping of the reverse sweep (frcnn_hip/train.py TrainState._sweep) -- which gradient buffer is masked in the producing
+"""CPU: the bookkeeping of the reverse sweep (frcnn_hip/sweep.py: Sweep behind TrainState._sweep, and the route rule dgrad_route) -- which gradient buffer is masked in the producing
 launch, which identity-shortcut gradient is borrowed instead of copied, where operand planes of dY are emitted, when a tensor that
 received an unmasked contribution still gets its relu_bwd pass -- run against plain torch-CPU stand-ins for the C-ABI entries and for
 the stream / event objects.  The stand-ins compute the same functions the entries document (a convolution, y = mask > 0 ? y : 0, ...),
@@ -245,6 +245,89 @@ class FakeSession(object):
         return self.buf("pair/" + name, (N, K))
 
 
+class Tracer(object):
+    """The ORDERED trace of a run on the stand-ins (FakeOps.log only counts): one [entry name, labels of its tensor / plane / stream /
+    event arguments, its scalar arguments] per ops call and per ev_record / st_wait_event / st_wait_stream / pinned_stream entry (that
+    one with ops.ws_scope).  A label is the FakeSession buffer's name and shape, y:<scope> (x:<scope> for the image), w: / grad_w: /
+    acc_w:<scope>, seed:<i>, a stream's or event's creation order; a view carries the label of its base."""
+
+    def __init__(self):
+        self.trace, self.sess, self.net, self.seeds, self.labels, self.made = [], None, None, [], None, {}
+        self.ops = ops = FakeOps()
+        for name in dir(FakeOps):
+            if not name.startswith("_") and name != "pinned_stream":
+                setattr(ops, name, self._traced(name, getattr(ops, name)))
+        tracer = self
+
+        class pinned_stream(FakeOps.pinned_stream):
+            def __init__(self, stream):
+                self.stream = stream
+
+            def __enter__(self):
+                tracer.trace.append(["pinned_stream", [tracer.label(self.stream)], [ops.ws_scope]])
+                return self
+        ops.pinned_stream = pinned_stream
+
+    def _traced(self, name, fn):
+        def call(*args, **kw):
+            labels, scalars = [], []
+            for key, v in [(None, a) for a in args] + sorted(kw.items()):
+                lab = self.label(v)
+                what = v if lab is None else lab
+                (scalars if lab is None else labels).append(what if key is None else "%s=%s" % (key, what))
+            self.trace.append([name, labels, scalars])
+            return fn(*args, **kw)
+        return call
+
+    def _make(self, kind, obj):
+        self.made[id(obj)] = (obj, "%s%d" % (kind, sum(1 for _, lab in self.made.values() if lab.startswith(kind))))
+        return obj
+
+    def stream(self, device=None):
+        return self._make("stream", FakeStream())
+
+    def event(self):
+        return self._make("event", FakeEvent())
+
+    def _known(self):
+        out = {}
+
+        def put(t, lab):
+            out.setdefault((t.untyped_storage().data_ptr(), t.storage_offset()), lab)
+            out.setdefault(t.untyped_storage().data_ptr(), lab)
+        for i, (_, g) in enumerate(self.seeds):
+            put(g, "seed:%d" % i)
+        for sc, p in self.net.params.items():
+            for field in ("grad_w", "w", "acc_w"):
+                put(getattr(p, field), "%s:%s" % (field, sc))
+        for rec in self.net._tape:
+            put(rec["y"], "y:" + rec["scope"])
+        for rec in self.net._tape:
+            put(rec["x"], "x:" + rec["scope"])
+        for key, t in self.sess.buffers.items():
+            put(t.t if isinstance(t, Planes) else t, " ".join(str(k) for k in key))
+        return out
+
+    def label(self, v):
+        """the label of a tensor, planes, stream, event or table argument; None for a scalar"""
+        if id(v) in self.made:
+            return self.made[id(v)][1]
+        if isinstance(v, Planes):
+            v = v.t
+        if isinstance(v, list) and v and isinstance(v[0], tuple):
+            return "table[%d]" % len(v)                      # the solver's descriptor table (built in apply(), not in the sweep)
+        if not isinstance(v, torch.Tensor):
+            return None
+        keys = ((v.untyped_storage().data_ptr(), v.storage_offset()), v.untyped_storage().data_ptr())
+        for attempt in (0, 1):
+            if self.labels is None or attempt:
+                self.labels = self._known()
+            for key in keys:
+                if key in self.labels:
+                    return self.labels[key]
+        return "?" + str(tuple(v.shape))
+
+
 class Net(object):
     """A small TRAIN graph in the reference's bottleneck shape (resnet_v1.py:80-113), forward values from torch, as a tape."""
 
@@ -309,13 +392,29 @@ def build(sess, seed):
     return net, [(h1, g1.clone()), (h2, g2.clone())]
 
 
-def run_sweep(monkeypatch, fuse, pipe, wino, h2_train, seed=0):
+def stand_ins(monkeypatch, tracer=None):
+    """(frcnn_hip.train, the stand-in ops, a FakeSession) with train.ops, torch.cuda.Stream and torch.cuda.Event replaced; tracer: a Tracer that also writes down the ordered trace"""
     from frcnn_hip import train
-    ops = FakeOps()
-    monkeypatch.setattr(train, "ops", ops)
-    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: FakeStream())
-    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
+    ops = FakeOps() if tracer is None else tracer.ops
+    monkeypatch.setattr(train, "ops", ops)                   # (TrainState hands its module's ops to the sweep: frcnn_hip/sweep.py makes no launch of its own)
+    monkeypatch.setattr(torch.cuda, "Stream", (lambda device=None: FakeStream()) if tracer is None else tracer.stream)
+    monkeypatch.setattr(torch.cuda, "Event", FakeEvent if tracer is None else tracer.event)
     sess = FakeSession()
+    if tracer is not None:
+        tracer.sess = sess
+    return train, ops, sess
+
+
+def begin_sweep(tracer, net, seeds):
+    """the main stream of one sweep; a tracer is told the sweep's tensors, to name them"""
+    if tracer is None:
+        return FakeStream()
+    tracer.net, tracer.seeds, tracer.labels = net, seeds, None
+    return tracer.stream()
+
+
+def run_sweep(monkeypatch, fuse, pipe, wino, h2_train, seed=0, tracer=None):
+    train, ops, sess = stand_ins(monkeypatch, tracer)
     net, seeds = build(sess, seed)
     ts = train.TrainState(sess, net)
     ts.params = net.params                                   # (the stand-in for build())
@@ -323,7 +422,7 @@ def run_sweep(monkeypatch, fuse, pipe, wino, h2_train, seed=0):
     ts.winograd = (4, 64, True) if wino else None
     ts.h2_train = h2_train
     ts.wgrad_stream, ts.wgrad_h2, ts.prep_stream = 2, True, False
-    ts._sweep(seeds, FakeStream())
+    ts._sweep(seeds, begin_sweep(tracer, net, seeds))
     return net, ops.log
 
 
@@ -350,6 +449,85 @@ def test_folded_passes_give_the_bits_of_the_separate_passes_and_the_gradients_of
     assert log0["wgrad"] == log1["wgrad"] == log2["wgrad"] == 13
 
 
+GRID = [(fuse, pipe, wino, h2_train) for fuse, pipe in ((False, False), (True, False), (True, True)) for wino in (False, True)
+        for h2_train in (None, 1)]
+
+
+def sweep_traces():
+    """{run: its ordered trace}: the grid of the test above, the three-step runs with and without the solver inside the sweep, the two
+    data-parallel runs (those with what the exchange was handed).  tests/golden/sweep_trace.json holds them as fixtures/gen_sweep_trace.py
+    wrote them."""
+    out = {}
+    for fuse, pipe, wino, h2_train in GRID:
+        with pytest.MonkeyPatch.context() as mp:
+            tr = Tracer()
+            run_sweep(mp, fuse, pipe, wino, h2_train, tracer=tr)
+            out["sweep fuse_chain=%d pipe_dgrads=%d winograd=%d h2_train=%s" % (fuse, pipe, wino, h2_train)] = tr.trace
+    for in_sweep in (False, True):
+        with pytest.MonkeyPatch.context() as mp:
+            tr = Tracer()
+            run_steps(mp, in_sweep, tracer=tr)
+            out["3 steps solver_in_sweep=%d" % in_sweep] = tr.trace
+        with pytest.MonkeyPatch.context() as mp:
+            tr = Tracer()
+            sends = run_dp_steps(mp, in_sweep, tracer=tr)[3]
+            out["3 data-parallel steps solver_in_sweep=%d" % in_sweep] = tr.trace + [["exchange", [], step] for step in sends]
+    return out
+
+
+def test_the_ordered_trace_of_every_run_is_the_recorded_one():
+    """Every ops call, event record, wait and pinned-stream entry of the runs above, in order, with the names of its buffers and its
+    scalar arguments, against the trace recorded from the sweep as it was before it was split into frcnn_hip/sweep.py: a reordered
+    launch, another buffer name, pad or residual argument, another side-stream turn shows here (the counts of FakeOps.log cannot see it)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "sweep_trace.json")) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(sweep_traces()))
+    assert sorted(got) == sorted(want)
+    for run in sorted(want):
+        assert len(got[run]) > 50
+        for i, (g, w) in enumerate(zip(got[run], want[run])):
+            assert g == w, (run, i, got[run][max(0, i - 2):i + 1], w)
+        assert len(got[run]) == len(want[run]), run
+
+
+ROUTE_SWITCHES = dict(winograd=dict(winograd=(4, 64, True)), flipped=dict(), h2=dict(h2_train=1), padded=dict(pipe_dgrads=True),
+                      upsampled=dict(pipe_dgrads=True), gather=dict(pipe_dgrads=True))
+
+
+def route_of(case, has_grad=False, pipe_dgrads=False, winograd=None, h2_train=None):
+    from frcnn_hip.sweep import dgrad_route
+    import dgrad_ref as R
+    _, N, H, W, Cin, Cout, k, stride, pad = case
+    OH, OW = R.conv_out(H, k, stride, pad[0], pad[1]), R.conv_out(W, k, stride, pad[2], pad[3])
+    return dgrad_route(k, stride, pad, Cin, Cout, H, W, N, OH, OW, 4, has_grad, pipe_dgrads, winograd, h2_train)
+
+
+def test_dgrad_route_answers_the_key_every_case_is_listed_under():
+    """oracle/dgrad_ref.CASES against the route rule (frcnn_hip/sweep.py dgrad_route), each case under the switches its key implies;
+    with every switch on, the priority order; and no Winograd into a tensor that holds a gradient when pipe_dgrads is off."""
+    import dgrad_ref as R
+    assert sum(len(c) for c in R.CASES.values()) == 32
+    for key, cases in R.CASES.items():
+        for case in cases:
+            sw = dict(pipe_dgrads=False) if case[0] == "3x3s2_9x13" else ROUTE_SWITCHES[key]
+            for has_grad in (False, True):
+                if key == "winograd" and has_grad:
+                    sw = dict(sw, pipe_dgrads=True)          # (Winograd + one add pass into a tensor that holds a gradient: only with pipe_dgrads)
+                route, m = route_of(case, has_grad, **sw)
+                assert route == key, (key, case[0], has_grad, route)
+                assert m == ((7 if case[2] == 7 and case[3] == 7 else 4) if key == "winograd" else None), (case[0], m)
+    every = dict(pipe_dgrads=True, winograd=(4, 64, True), h2_train=1)
+    flipped, gather = ({case[0]: case for case in R.CASES[key]} for key in ("flipped", "gather"))
+    for cid in ("3x3_37x63", "3x3_17x26", "3x3_1x40", "3x3_roi37"):
+        assert route_of(flipped[cid], **every)[0] == "winograd", cid
+    assert route_of(flipped["1x1_roi256"], **every)[0] == "h2"
+    assert route_of(gather["3x3s2_9x13"], **every)[0] == "upsampled"
+    for cases in R.CASES.values():
+        for case in cases:
+            assert route_of(case, True, pipe_dgrads=False, winograd=(4, 64, True), h2_train=1)[0] != "winograd", case[0]
+
+
 def test_a_tensor_with_an_unmasked_contribution_keeps_its_relu_pass(monkeypatch):
     """B's input feeds conv1 (masked data gradient) AND the projection shortcut; whichever lands second accumulates -- the sum must end up
     masked exactly once more or already be masked; the heads' two data gradients into the trunk output likewise.  Checked through the
@@ -361,14 +539,9 @@ def test_a_tensor_with_an_unmasked_contribution_keeps_its_relu_pass(monkeypatch)
     assert log1.get("relu_bwd", 0) <= 1 < log0["relu_bwd"]          # every contribution came masked out of its launch
 
 
-def run_steps(monkeypatch, in_sweep, steps=3, chunk=3):
+def run_steps(monkeypatch, in_sweep, steps=3, chunk=3, tracer=None):
     """`steps` x (reverse sweep + solver) on one tape: the in-sweep solver updates ranges of the descriptor table while the sweep goes on"""
-    from frcnn_hip import train
-    ops = FakeOps()
-    monkeypatch.setattr(train, "ops", ops)
-    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: FakeStream())
-    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
-    sess = FakeSession()
+    train, ops, sess = stand_ins(monkeypatch, tracer)
     net, seeds = build(sess, 5)
     ts = train.TrainState(sess, net, momentum=0.9, weight_decay=1e-4)
     ts.params = net.params
@@ -378,7 +551,8 @@ def run_steps(monkeypatch, in_sweep, steps=3, chunk=3):
     order = []
     for _ in range(steps):
         ops.updated = []
-        ts._sweep([(t, g.clone()) for t, g in seeds], FakeStream(), in_sweep)
+        step_seeds = [(t, g.clone()) for t, g in seeds]
+        ts._sweep(step_seeds, begin_sweep(tracer, net, step_seeds), in_sweep)
         ts.apply(ts.lr)
         order.append(list(ops.updated))
     return net, ops.log, order
@@ -439,13 +613,8 @@ class FakeExchange(object):
         return flat
 
 
-def run_dp_steps(monkeypatch, in_sweep, steps=3, chunk=3, bucket=40000):
-    from frcnn_hip import train
-    ops = FakeOps()
-    monkeypatch.setattr(train, "ops", ops)
-    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: FakeStream())
-    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
-    sess = FakeSession()
+def run_dp_steps(monkeypatch, in_sweep, steps=3, chunk=3, bucket=40000, tracer=None):
+    train, ops, sess = stand_ins(monkeypatch, tracer)
     net, seeds = build(sess, 5)
     total = sum(p.grad_w.numel() for p in net.params.values())
     flat, off = torch.zeros(total), 0
@@ -462,7 +631,8 @@ def run_dp_steps(monkeypatch, in_sweep, steps=3, chunk=3, bucket=40000):
     order, sends = [], []
     for _ in range(steps):
         ops.updated, ts.all_reduce.log = [], []
-        ts._sweep([(t, g.clone()) for t, g in seeds], FakeStream(), in_sweep)
+        step_seeds = [(t, g.clone()) for t, g in seeds]
+        ts._sweep(step_seeds, begin_sweep(tracer, net, step_seeds), in_sweep)
         ts.apply(ts.lr, world_size=2, all_reduce=ts.all_reduce)
         order.append(list(ops.updated))
         sends.append(list(ts.all_reduce.log))
@@ -504,12 +674,7 @@ OTHER = dict(fuse_chain=False, pipe_dgrads=False, prep_stream=False, solver_in_s
 
 
 def handle(monkeypatch, seed=0):
-    from frcnn_hip import train
-    ops = FakeOps()
-    monkeypatch.setattr(train, "ops", ops)
-    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: FakeStream())
-    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
-    sess = FakeSession()
+    train, ops, sess = stand_ins(monkeypatch)
     net, seeds = build(sess, seed)
     ts = train.TrainState(sess, net)
     ts.params.update(net.params)                             # (what build() fills)

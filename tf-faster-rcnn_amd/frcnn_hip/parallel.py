@@ -124,7 +124,7 @@ class BucketedAllReduce(object):
         self.final_from = None
         self.handles = []
 
-    multi_stream = True                # ready() takes every stream the gradients may have been enqueued on (TrainState._sweep: two side streams)
+    multi_stream = True                # ready() takes every stream the gradients may have been enqueued on (sweep.Sweep.on_side: two side streams)
 
     def _order_after(self, streams):
         """One stream that is behind everything enqueued so far on `streams`: the collective is issued with it current (torch.distributed

@@ -312,6 +312,39 @@ size_t frcnn_jpeg_workspace_bytes(int width, int height, int ncomp, int hs, int 
 int frcnn_jpeg_pixels(const void* coef_d, int width, int height, int ncomp, int hs, int vs, unsigned char* bgr_d, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* Baseline JPEG encode, the mirror (csrc/jpeg_encode_host.h + csrc/jpeg_encode.hip; additive, FRCNN_ABI_VERSION unchanged): BGR uint8
+ * [h][w][3] -> the SAME coefficient buffer the decoder reads (three components, luma 1x1 / 2x1 / 2x2; frcnn_jpeg_coef_bytes(width,
+ * height, 3, hs, vs) bytes) in two launches -- colour conversion + downsampling into the sample planes, then jfdctint + quantisation -- and
+ * from its host copy a complete baseline file on the HOST.  libjpeg's integer rules: the coefficients equal those of PIL's encoder (same
+ * quality and subsampling) bit for bit.  quality 1..100 (libjpeg's scaling of the Annex K tables).
+ *   frcnn_jpeg_quant_tables:   HOST. out128 = uint16 [2][64], luminance then chrominance, natural order
+ *   frcnn_jpeg_coefs:          bgr_d (any address) -> coef_d (2-byte aligned; 16-byte aligned for the wide stores); ws (16-byte aligned) of
+ *                              frcnn_jpeg_workspace_bytes(width, height, 3, hs, vs) bytes; ws_bytes too small: FRCNN_E_ARG, nothing launched
+ *   frcnn_jpeg_coefs_host:     HOST statement of frcnn_jpeg_coefs (the same arithmetic header)
+ *   frcnn_jpeg_stream_bound:   HOST. an upper bound of the file's size; 0 for a geometry outside the list
+ *   frcnn_jpeg_entropy_encode: HOST, thread-safe, no allocation.  coef_h -> SOI, JFIF APP0, DQT, SOF0, the four Annex K Huffman tables, one
+ *                              interleaved scan without restart markers, EOI; returns the bytes written, or FRCNN_E_ARG (cap too small, a
+ *                              table entry outside 1..255, a coefficient outside baseline's range); nothing is written at or beyond out + cap */
+int frcnn_jpeg_quant_tables(int quality, unsigned short* out128);
+int frcnn_jpeg_coefs(const unsigned char* bgr_d, int width, int height, int hs, int vs, int quality, void* coef_d, void* ws,
+                     size_t ws_bytes, void* stream);
+int frcnn_jpeg_coefs_host(const unsigned char* bgr_h, int width, int height, int hs, int vs, int quality, void* coef_h);
+size_t frcnn_jpeg_stream_bound(int width, int height, int hs, int vs);
+long long frcnn_jpeg_entropy_encode(const void* coef_h, int width, int height, int hs, int vs, unsigned char* out, size_t cap);
+
+/* Detections drawn on a BGR uint8 image [h][w][3] in place (csrc/draw_math.h states the rule, csrc/draw.hip runs it): for each record
+ * k < min(count, max_dets) of dets [max_dets][6] = (x1, y1, x2, y2, score, class) with score >= conf, an outline of `thickness` pixels in
+ * colours[class % num_colours] (BGR) and a label plate "<class name> d.ddd" in a 5 x 7 bitmap font magnified by `scale`; later records
+ * paint over earlier ones.  frcnn_draw_detections takes the records and the DEVICE-RESIDENT count as frcnn_detect_post leaves them.
+ * labels [num_classes][label_stride] (NUL-padded names), glyphs [95][7] (printable ASCII, a row's bit 4 = its left column).  NaN or far
+ * coordinates, empty boxes and classes outside [0, num_classes) are skipped.  thickness 1..64, scale 1..16, label_stride 1..64. */
+int frcnn_draw_detections(unsigned char* bgr_d, int h, int w, const float* dets_d, const int* cnt_d, int max_dets, float conf,
+                          int thickness, int scale, const unsigned char* colours_d, int num_colours, const unsigned char* labels_d,
+                          int num_classes, int label_stride, const unsigned char* glyphs_d, void* stream);
+int frcnn_draw_detections_host(unsigned char* bgr_h, int h, int w, const float* dets_h, int count, int max_dets, float conf,
+                               int thickness, int scale, const unsigned char* colours_h, int num_colours, const unsigned char* labels_h,
+                               int num_classes, int label_stride, const unsigned char* glyphs_h);
+
 /* G independent NT GEMMs in one launch (f32 MFMA): y[g][m][n] = sum_k x[g][m][k] * w[g][n][k];  K % 32 == 0. */
 int frcnn_gemm_batched_nt(const float* x_d, const float* w_d, float* y_d, int G, int M, int N, int K, void* stream);
 /* f32 "NT" GEMM on the bf16 matrix pipe with exactly split operands (csrc/gemm_x3.hip; cfg.HIP.MFMA_X3, default on in TEST mode; finite operands below the bf16 maximum -- an inf operand yields NaN, not inf): every f32 value

@@ -146,3 +146,105 @@ JPEG_HD bool jpeg_geom(int w, int h, int ncomp, int hs, int vs, JpegGeom* g) {
   g->coef_bytes = 384 + (size_t)nblk * 128;
   return true;
 }
+
+// ---- the forward direction (csrc/jpeg_encode.hip, jpeg_host::coefs_host): BGR -> the same coefficient buffer, libjpeg's integer rules of
+// jccolor / jcsample (no smoothing) / jfdctint / jcdctmgr, so that the coefficients equal those of PIL's own encoder bit for bit ----------
+
+JPEG_HD void jpeg_bgr_to_ycc(int b, int g, int r, int* y, int* cb, int* cr) {
+  *y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+  *cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+  *cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// The padding order of libjpeg's preprocessing controller, as indices: the input pixels that make up sample (sx, sy) of component c's
+// MCU-padded plane.  Columns are replicated on the INPUT out to the padded width; rows are replicated on the input up to a multiple of vs,
+// and below that the DOWNSAMPLED last row is replicated -- so a chroma row below the cropped plane (ch rows) is row ch - 1 again, NOT the
+// mean of two copies of the last input row (an 8 x 8 image at 4:2:0 shows the difference).  Luma rows are plain replication either way.
+JPEG_HD int jpeg_src_col(int x, int w) { return x < w ? x : w - 1; }
+JPEG_HD int jpeg_luma_src_row(int sy, int h) { return sy < h ? sy : h - 1; }
+JPEG_HD int jpeg_chroma_src_row(int cy, int ch) { return cy < ch ? cy : ch - 1; }      // then rows vs * that + {0 .. vs - 1}, each clamped to h - 1
+
+// h2v1: (a + b + bias) >> 1, bias 0, 1, 0, 1, ... along the row; h2v2: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2, ...
+JPEG_HD int jpeg_down_h2v1(int a, int b, int cx) { return (a + b + (cx & 1)) >> 1; }
+JPEG_HD int jpeg_down_h2v2(int a, int b, int c, int d, int cx) { return (a + b + c + d + 1 + (cx & 1)) >> 2; }
+
+// One 8-point pass of jfdctint (CONST_BITS 13, PASS1_BITS 2).  FIRST: the row pass on samples - 128 (outputs 0 and 4 scaled up by 2 bits, the
+// others descaled by 11); else the column pass (0 and 4 descaled by 2, the others by 15).  uint32 sums like jpeg_idct_1d.
+template <bool FIRST>
+JPEG_HD void jpeg_fdct_1d(const int* in, int* out) {
+  typedef uint32_t u;
+  const u d0 = (u)in[0], d1 = (u)in[1], d2 = (u)in[2], d3 = (u)in[3], d4 = (u)in[4], d5 = (u)in[5], d6 = (u)in[6], d7 = (u)in[7];
+  const u tmp0 = d0 + d7, tmp7 = d0 - d7, tmp1 = d1 + d6, tmp6 = d1 - d6, tmp2 = d2 + d5, tmp5 = d2 - d5, tmp3 = d3 + d4, tmp4 = d3 - d4;
+  const u tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  const int sh = FIRST ? 11 : 15;
+  const u rnd = 1u << (sh - 1);
+  if (FIRST) {
+    out[0] = (int)((tmp10 + tmp11) << 2), out[4] = (int)((tmp10 - tmp11) << 2);
+  } else {
+    out[0] = (int)(tmp10 + tmp11 + 2u) >> 2, out[4] = (int)(tmp10 - tmp11 + 2u) >> 2;
+  }
+  u z1 = (tmp12 + tmp13) * 4433u;                               // FIX_0_541196100
+  out[2] = (int)(z1 + tmp13 * 6270u + rnd) >> sh;               // FIX_0_765366865
+  out[6] = (int)(z1 + tmp12 * (u)-15137 + rnd) >> sh;           // -FIX_1_847759065
+  z1 = tmp4 + tmp7;
+  u z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+  const u z5 = (z3 + z4) * 9633u;                               // FIX_1_175875602
+  const u t4 = tmp4 * 2446u, t5 = tmp5 * 16819u, t6 = tmp6 * 25172u, t7 = tmp7 * 12299u;
+  z1 *= (u)-7373, z2 *= (u)-20995;
+  z3 = z3 * (u)-16069 + z5, z4 = z4 * (u)-3196 + z5;
+  out[7] = (int)(t4 + z1 + z3 + rnd) >> sh, out[5] = (int)(t5 + z2 + z4 + rnd) >> sh;
+  out[3] = (int)(t6 + z2 + z3 + rnd) >> sh, out[1] = (int)(t7 + z1 + z4 + rnd) >> sh;
+}
+
+// n / d, truncating, for 0 <= n < 2^22 and 1 <= d <= 2040 WITHOUT an integer divide (the device has no such instruction): the float
+// quotient is within one of the true one (n, d and the quotient are all exact in 24 bits; one rounding in 1 / d, one in the product),
+// and two comparisons settle it.  csrc/jpeg_encode_host_check.cc compares it with `/` for every n the DCT can produce and every d.
+JPEG_HD int jpeg_div_trunc(int n, int d, float rd) {
+  int q = (int)((float)n * rd);
+  if (q * d > n) --q;
+  if ((q + 1) * d <= n) ++q;
+  return q;
+}
+
+// jcdctmgr's rounding division of a DCT output (scaled by 8) by qv = 8 q: symmetric about zero.
+JPEG_HD int jpeg_quantise(int c, int q, float rd) {
+  const int qv = q << 3, half = qv >> 1;
+  return c >= 0 ? jpeg_div_trunc(c + half, qv, rd) : -jpeg_div_trunc(half - c, qv, rd);
+}
+JPEG_HD float jpeg_quant_rcp(int q) { return 1.0f / (float)(q << 3); }
+
+// The host's form of a whole block: samples [8][pitch] -> quantised coefficients [64], natural order.
+JPEG_HD void jpeg_fdct_block(const unsigned char* s, int pitch, const uint16_t* quant, int16_t* coef) {
+  int ws[64];
+  for (int r = 0; r < 8; ++r) {
+    int in[8];
+    for (int c = 0; c < 8; ++c) in[c] = (int)s[(size_t)r * pitch + c] - 128;
+    jpeg_fdct_1d<true>(in, ws + r * 8);
+  }
+  for (int c = 0; c < 8; ++c) {
+    int in[8], o[8];
+    for (int r = 0; r < 8; ++r) in[r] = ws[r * 8 + c];
+    jpeg_fdct_1d<false>(in, o);
+    for (int r = 0; r < 8; ++r) coef[r * 8 + c] = (int16_t)jpeg_quantise(o[r], quant[r * 8 + c], jpeg_quant_rcp(quant[r * 8 + c]));
+  }
+}
+
+// Luma blocks that pad an MCU beyond the component's real blocks (rbx x rby of them) carry no samples: all AC zero, DC that of the block
+// before it in the MCU -- at the right edge the block to its left, in a bottom row the LAST block of the row above within the same MCU
+// (itself possibly a right-edge dummy).  Every dummy therefore resolves to ONE real block; returns whether (brow, bcol) is a dummy and
+// writes that block's position.  Chroma has no dummies (one block per MCU).
+JPEG_HD bool jpeg_dummy_source(int brow, int bcol, int hs, int rbx, int rby, int* srow, int* scol) {
+  int r = brow, c = bcol;
+  if (r >= rby) r -= 1, c = (c / hs) * hs + hs - 1;
+  if (c >= rbx) c -= 1;
+  *srow = r, *scol = c;
+  return r != brow || c != bcol;
+}
+
+// libjpeg's quality scaling (jpeg_quality_scaling + jpeg_add_quant_table, force_baseline) of the Annex K tables, natural order.
+JPEG_HD int jpeg_quality_entry(int base, int quality) {
+  quality = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  const int v = (base * s + 50) / 100;
+  return v < 1 ? 1 : (v > 255 ? 255 : v);
+}

@@ -82,7 +82,14 @@ SIGNATURES = {
     "frcnn_jpeg_pixels_host": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "frcnn_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "frcnn_jpeg_pixels": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
-    "frcnn_gemm_batched_nt": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "frcnn_jpeg_quant_tables": (c_int, [c_int, _P]),
+    "frcnn_jpeg_coefs": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "frcnn_jpeg_coefs_host": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "frcnn_jpeg_stream_bound": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "frcnn_jpeg_entropy_encode": (c_longlong, [_P, c_int, c_int, c_int, c_int, _P, c_size_t]),
+    "frcnn_draw_detections": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_float, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
+    "frcnn_draw_detections_host": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_float, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    "frcnn_gemm_batched_nt": (c_int,[_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "frcnn_winograd_filter_transform": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "frcnn_winograd_filter_transform_device": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "frcnn_winograd_input_transform": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),

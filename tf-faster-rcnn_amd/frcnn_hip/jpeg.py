@@ -7,7 +7,11 @@ went: PIL on the host, then the copy; the user sees PIL's pixels or PIL's error.
 
 decode_bgr: one file, synchronous.  JpegCache / JpegPrefetcher: worker threads read files and entropy-decode into a pool of pinned
 buffers ahead of the consumer, which issues the copy and the two launches on ITS current stream; a pinned buffer is written again only
-after an event recorded behind its copy has completed."""
+after an event recorded behind its copy has completed.
+
+The other direction mirrors it: encode_bgr / JpegWriter turn a BGR tensor into a baseline JPEG file -- colour conversion, downsampling, DCT
+and quantisation in two kernels (frcnn_jpeg_coefs) into the SAME coefficient buffer, the Huffman stage on the host
+(frcnn_jpeg_entropy_encode).  The coefficients equal those of PIL's encoder at the same quality and subsampling bit for bit."""
 import io
 from concurrent.futures import ThreadPoolExecutor
 
@@ -140,6 +144,90 @@ class JpegCache(object):
             fut.cancel()
         self._pool.shutdown(wait=True)
         self._pending = {}
+
+
+def encode_bgr(im, quality=90, subsampling=2):
+    """BGR uint8 [h,w,3] -> the bytes of a baseline JPEG file whose coefficients are those of PIL's encoder at the same quality and
+    subsampling (0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0).  A device tensor: colour conversion, downsampling, DCT and quantisation in two launches,
+    the coefficient buffer copied to the host, the Huffman stage there.  A CPU tensor or numpy array: the host statement of the kernels."""
+    if torch.is_tensor(im) and im.is_cuda:
+        coef = ops.jpeg_coefs(im, quality, subsampling).cpu()
+    else:
+        coef = ops.jpeg_coefs_host(im, quality, subsampling)
+    return ops.jpeg_entropy_encode(coef, ops.jpeg_encode_geom(im.shape[0], im.shape[1], subsampling))
+
+
+class _WSlot(object):
+    __slots__ = ("buf", "ev", "fut")
+
+    def __init__(self):
+        self.buf, self.ev, self.fut = None, None, None
+
+
+class JpegWriter(object):
+    """The counterpart of JpegCache: submit(path, im_d) launches the two encode kernels on the caller's current stream, copies the
+    coefficient buffer into one of `depth` pinned buffers and records an event; a worker thread waits for the event, runs the Huffman stage
+    (C, the GIL released) and writes the file.  A pinned buffer is used again only after its file has been written.  An exception of a worker
+    (an unwritable path, say) is raised by the next submit() or by close()."""
+
+    MIN_SLOT_BYTES = 1 << 20
+
+    def __init__(self, device, workers=4, depth=8):
+        self.device = torch.device(device)
+        self._cuda = _is_cuda(device)
+        self._pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)))
+        self._slots = [_WSlot() for _ in range(max(1, int(depth)))]
+        self._k = 0
+        self._errors = []
+
+    def _work(self, path, slot, nbytes, geom):
+        if slot.ev is not None:
+            slot.ev.synchronize()                                # the copy into this buffer has finished
+        data = ops.jpeg_entropy_encode(slot.buf[:nbytes], geom)
+        with open(path, "wb") as f:
+            f.write(data)
+
+    def _reap(self, slot):
+        """wait until the slot's file is written; keep a worker's exception for _raise"""
+        fut, slot.fut = slot.fut, None
+        if fut is not None:
+            try:
+                fut.result()
+            except Exception as e:                               # noqa: BLE001  (re-raised by _raise)
+                self._errors.append(e)
+
+    def _raise(self):
+        if self._errors:
+            e, self._errors = self._errors[0], []
+            raise e
+
+    def submit(self, path, im, quality=90, subsampling=2):
+        for s in self._slots:                                    # whatever has finished by now, without waiting
+            if s.fut is not None and s.fut.done():
+                self._reap(s)
+        self._raise()
+        slot = self._slots[self._k]
+        self._k = (self._k + 1) % len(self._slots)
+        self._reap(slot)
+        self._raise()
+        geom = ops.jpeg_encode_geom(im.shape[0], im.shape[1], subsampling)
+        n = ops.jpeg_coef_bytes(geom)
+        if slot.buf is None or slot.buf.numel() < n:
+            slot.buf = torch.empty(max(n, self.MIN_SLOT_BYTES), dtype=torch.uint8, pin_memory=self._cuda)
+        if self._cuda:
+            slot.buf[:n].copy_(ops.jpeg_coefs(im, quality, subsampling), non_blocking=True)
+            if slot.ev is None:
+                slot.ev = torch.cuda.Event()
+            slot.ev.record(torch.cuda.current_stream())
+        else:
+            ops.jpeg_coefs_host(im, quality, subsampling, out=slot.buf)
+        slot.fut = self._pool.submit(self._work, path, slot, n, geom)
+
+    def close(self):
+        for s in self._slots:
+            self._reap(s)
+        self._pool.shutdown(wait=True)
+        self._raise()
 
 
 class JpegPrefetcher(object):

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 import frcnn_hip as _binding
-from . import ACT_NONE, NMS_RULE_CPU, call, lib
+from . import ACT_NONE, NMS_RULE_CPU, call, check, lib
 
 _ws_cache = {}
 ws_scope = "default"     # set by callers that run several independent chains concurrently (one scope per stream)
@@ -634,6 +634,108 @@ def jpeg_pixels(coef_d, geom, out=None):
     ws = workspace(int(lib().frcnn_jpeg_workspace_bytes(w, h, int(geom[2]), int(geom[3]), int(geom[4]))), coef_d.device, tag="jpeg")
     call("frcnn_jpeg_pixels", _ptr(coef_d), w, h, int(geom[2]), int(geom[3]), int(geom[4]), _ptr(out), _ptr(ws), ws.numel(), _stream())
     return out
+
+
+# ---- baseline JPEG encode, the mirror: device colour + downsampling + DCT, host Huffman stage (csrc/jpeg_encode.hip, csrc/jpeg_encode_host.h)
+JPEG_SAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2)}            # PIL's `subsampling` -> luma (hs, vs)
+
+
+def jpeg_encode_geom(h, w, subsampling=2):
+    """(width, height, 3, hs, vs): the geometry tuple of a BGR [h,w,3] image encoded at PIL's `subsampling` 0 / 1 / 2"""
+    hs, vs = JPEG_SAMPLING[int(subsampling)]
+    return (int(w), int(h), 3, hs, vs)
+
+
+def jpeg_quant_tables(quality):
+    """HOST: uint16 [2,64], luminance then chrominance in natural order, libjpeg's scaling of the Annex K tables"""
+    out = np.empty((2, 64), dtype=np.uint16)
+    check(lib().frcnn_jpeg_quant_tables(int(quality), out.ctypes.data), "frcnn_jpeg_quant_tables")
+    return out
+
+
+def _coef_geom(geom):
+    n = jpeg_coef_bytes(geom)
+    if n == 0:
+        raise JpegError("frcnn_jpeg_coef_bytes", JPEG_E_UNSUPPORTED)
+    return n
+
+
+def jpeg_coefs_host(im, quality=90, subsampling=2, out=None):
+    """HOST statement of jpeg_coefs: BGR uint8 [h,w,3] (numpy or CPU tensor) -> the coefficient buffer, a host uint8 tensor."""
+    a = np.ascontiguousarray(im.numpy() if torch.is_tensor(im) else im, dtype=np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 3
+    geom = jpeg_encode_geom(a.shape[0], a.shape[1], subsampling)
+    n = _coef_geom(geom)
+    out = torch.empty(n, dtype=torch.uint8) if out is None else out
+    assert out.dtype == torch.uint8 and out.is_contiguous() and not out.is_cuda and out.numel() >= n
+    rc = lib().frcnn_jpeg_coefs_host(a.ctypes.data, geom[0], geom[1], geom[3], geom[4], int(quality), out.data_ptr())
+    if rc != 0:
+        raise JpegError("frcnn_jpeg_coefs_host", rc)
+    return out[:n]
+
+
+def jpeg_coefs(im_d, quality=90, subsampling=2, out=None):
+    """BGR uint8 [h,w,3] on the device -> the coefficient buffer on the device (uint8; `out`: at least jpeg_coef_bytes bytes at an even
+    address), two launches on the current stream."""
+    assert im_d.is_cuda and im_d.dtype == torch.uint8 and im_d.is_contiguous() and im_d.dim() == 3 and im_d.shape[2] == 3
+    geom = jpeg_encode_geom(im_d.shape[0], im_d.shape[1], subsampling)
+    n = _coef_geom(geom)
+    out = _empty((n,), dtype=torch.uint8, device=im_d.device) if out is None else out
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
+    ws = workspace(int(lib().frcnn_jpeg_workspace_bytes(*geom)), im_d.device, tag="jpeg_enc")
+    call("frcnn_jpeg_coefs", _ptr(im_d), geom[0], geom[1], geom[3], geom[4], int(quality), _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out[:n]
+
+
+def jpeg_stream_bound(geom):
+    return int(lib().frcnn_jpeg_stream_bound(int(geom[0]), int(geom[1]), int(geom[3]), int(geom[4])))
+
+
+def jpeg_entropy_encode(coef, geom, out=None):
+    """HOST: the Huffman stage of the encoder, coefficient buffer (host uint8 tensor) -> the bytes of a complete baseline JPEG file.  `out`: a
+    numpy uint8 scratch array of at least jpeg_stream_bound(geom) bytes (e.g. one per worker thread).  ctypes releases the GIL for the call."""
+    assert not coef.is_cuda and coef.dtype == torch.uint8 and coef.is_contiguous() and coef.numel() >= _coef_geom(geom)
+    cap = jpeg_stream_bound(geom)
+    out = np.empty(cap, dtype=np.uint8) if out is None else out
+    assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= cap
+    n = lib().frcnn_jpeg_entropy_encode(coef.data_ptr(), int(geom[0]), int(geom[1]), int(geom[3]), int(geom[4]), out.ctypes.data, out.size)
+    if n < 0:
+        raise JpegError("frcnn_jpeg_entropy_encode", int(n))
+    return out[:n].tobytes()
+
+
+# ---- detections drawn on the image (csrc/draw_math.h, csrc/draw.hip) ------------------------------------------------------------------
+def _draw_tables_ok(colours, labels, glyphs):
+    assert colours.dtype == torch.uint8 and colours.dim() == 2 and colours.shape[1] == 3 and colours.is_contiguous()
+    assert labels.dtype == torch.uint8 and labels.dim() == 2 and labels.is_contiguous()
+    assert glyphs.dtype == torch.uint8 and tuple(glyphs.shape) == (95, 7) and glyphs.is_contiguous()
+
+
+def draw_detections(im_d, dets_d, cnt_d, conf, thickness, scale, colours_d, labels_d, glyphs_d):
+    """In place on im_d (BGR uint8 [h,w,3], device): the records dets_d [max_dets,6] and their device-resident count cnt_d [1] int32, as
+    detect_post leaves them.  colours_d [n,3] BGR, labels_d [num_classes,stride] NUL-padded names, glyphs_d [95,7]: uint8 device tensors."""
+    assert im_d.is_cuda and im_d.dtype == torch.uint8 and im_d.is_contiguous() and im_d.dim() == 3 and im_d.shape[2] == 3
+    assert dets_d.is_cuda and dets_d.dtype == torch.float32 and dets_d.dim() == 2 and dets_d.shape[1] == 6 and dets_d.is_contiguous()
+    assert cnt_d.is_cuda and cnt_d.dtype == torch.int32 and cnt_d.numel() >= 1
+    _draw_tables_ok(colours_d, labels_d, glyphs_d)
+    assert colours_d.is_cuda and labels_d.is_cuda and glyphs_d.is_cuda
+    call("frcnn_draw_detections", _ptr(im_d), int(im_d.shape[0]), int(im_d.shape[1]), _ptr(dets_d), _ptr(cnt_d), int(dets_d.shape[0]),
+         float(conf), int(thickness), int(scale), _ptr(colours_d), int(colours_d.shape[0]), _ptr(labels_d), int(labels_d.shape[0]),
+         int(labels_d.shape[1]), _ptr(glyphs_d), _stream())
+    return im_d
+
+
+def draw_detections_host(im, dets, count, conf, thickness, scale, colours, labels, glyphs):
+    """HOST statement of draw_detections, in place on the numpy uint8 [h,w,3] image `im`; dets float32 [max_dets,6] numpy, count an int;
+    the tables CPU uint8 tensors."""
+    assert isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.flags["C_CONTIGUOUS"]
+    dets = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 6)
+    _draw_tables_ok(colours, labels, glyphs)
+    assert not (colours.is_cuda or labels.is_cuda or glyphs.is_cuda)
+    check(lib().frcnn_draw_detections_host(im.ctypes.data, im.shape[0], im.shape[1], dets.ctypes.data, int(count), dets.shape[0], float(conf),
+                                           int(thickness), int(scale), colours.data_ptr(), colours.shape[0], labels.data_ptr(),
+                                           labels.shape[0], labels.shape[1], glyphs.data_ptr()), "frcnn_draw_detections_host")
+    return im
 
 
 def winograd_filter_transform(w_hwio, scale=None, m=2):

@@ -225,4 +225,6 @@ NO_STREAM_ARG = frozenset(["frcnn_set_tuning", "frcnn_detect_set_tuning", "frcnn
 HOST_ONLY = frozenset(["frcnn_generate_anchors", "frcnn_winograd_filter_transform", "frcnn_winograd7_filter_transform", "frcnn_pack_filter_hwio",
                        "frcnn_prep_image_shape", "frcnn_crc32c", "frcnn_snappy_uncompress", "_nms", "frcnn_graph_begin", "frcnn_graph_end",
                        "frcnn_graph_launch", "frcnn_graph_destroy", "frcnn_abi_version", "frcnn_build_info", "frcnn_sgd_desc_bytes",
-                       "frcnn_conv2d_wgrad_supported", "frcnn_jpeg_info", "frcnn_jpeg_entropy_decode", "frcnn_jpeg_pixels_host", "frcnn_summary_limits"])
+                       "frcnn_conv2d_wgrad_supported", "frcnn_jpeg_info", "frcnn_jpeg_entropy_decode", "frcnn_jpeg_pixels_host", "frcnn_summary_limits",
+                       "frcnn_jpeg_quant_tables", "frcnn_jpeg_coefs_host", "frcnn_jpeg_stream_bound", "frcnn_jpeg_entropy_encode",
+                       "frcnn_draw_detections_host"])

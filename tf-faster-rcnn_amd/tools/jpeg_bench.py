@@ -12,6 +12,10 @@ warm-up, with a few hundred decodes per timing window.
               process, three repeats each.  --batch N [N ...]: the same files through model.test.detect_paths_batched (the loop of
               test_net_imdb under cfg.HIP.TEST_BATCH_IMAGES = N; 1 = the detect_bgr loop above), every (N, switch) pair alternated in
               the same process (profiles/test_net_batched.txt).
+  --encode    the other direction (profiles/demo_annotate.txt): 375 x 500 and 600 x 1000 images with 30 seeded boxes, quality 90, 4:2:0.
+              The draw launch and the two encode launches between HIP events, the host Huffman stage per image, and files per second of
+              draw + JpegWriter (4 workers) against the host path -- D2H copy, PIL draw, PIL save -- on 1 and 4 threads, alternated
+              (--files per run; --files 0: the launches alone, the process to put under `rocprofv3 --kernel-trace --stats`).
 """
 import argparse
 import io
@@ -220,9 +224,119 @@ def _e2e_runs(args, sess, net, paths):
             print("  prep + chain + post + deferred read-back, batch %d, no decode : %s" % (b, alone(chain_only)))
 
 
+ENCODE_SIZES = ((375, 500), (600, 1000))
+ENCODE_CLASSES = ("__background__", "aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog",
+                  "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
+
+
+def _boxes(h, w, n, seed):
+    """n seeded detection records [n,6] inside an h x w image, scores 0.8 .. 1"""
+    rng = np.random.RandomState(seed)
+    x1, y1 = rng.uniform(0, w * 0.7, n), rng.uniform(0, h * 0.7, n)
+    return np.stack([x1, y1, x1 + rng.uniform(20, w * 0.3, n), y1 + rng.uniform(20, h * 0.3, n), rng.uniform(0.8, 1.0, n),
+                     rng.randint(1, 21, n)], axis=1).astype(np.float32)
+
+
+def _pil_annotate(bgr, dets, path, quality):
+    """the host path of today: PIL draws the boxes and labels on the image read back from the device, PIL encodes"""
+    from PIL import Image, ImageDraw, ImageFont
+    from utils.visualization import COLORS
+    pic = Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1]))
+    draw, font = ImageDraw.Draw(pic), ImageFont.load_default()
+    for x1, y1, x2, y2, s, c in dets:
+        colour = COLORS[int(c) % len(COLORS)]
+        draw.rectangle([x1, y1, x2, y2], outline=colour, width=2)
+        label = "%s %.3f" % (ENCODE_CLASSES[int(c)], s)
+        l, t, r, b = draw.textbbox((0, 0), label, font=font)
+        ty = y1 - (b - t) - 4 if y1 - (b - t) - 4 >= 0 else y1
+        draw.rectangle([x1, ty, x1 + r - l + 4, ty + b - t + 4], fill=colour)
+        draw.text((x1 + 2, ty + 2 - t), label, fill=(0, 0, 0), font=font)
+    pic.save(path, "JPEG", quality=quality)
+
+
+def encode_bench(args):
+    """--encode: the annotate-and-write half of tools/demo.py (profiles/demo_annotate.txt)"""
+    import torch
+    from frcnn_hip import jpeg, ops
+    from utils.visualization import draw_detections
+    dev = torch.device("cuda", 0)
+    quality, ndet = 90, 30
+    tmp = tempfile.mkdtemp(prefix="jpeg_bench_enc_")
+    try:
+        for (h, w) in ENCODE_SIZES:
+            base = torch.from_numpy(np.ascontiguousarray(np.asarray(picture(h, w, h))[:, :, ::-1])).to(dev)
+            dets = _boxes(h, w, ndet, h)
+            dets_d, cnt_d = torch.from_numpy(dets).to(dev), torch.tensor([ndet], dtype=torch.int32, device=dev)
+            im_d = base.clone()
+            geom = ops.jpeg_encode_geom(h, w, 2)
+
+            def events(fn):
+                for _ in range(20):
+                    fn()
+                torch.cuda.synchronize()
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+                for _ in range(args.n):
+                    fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                return ev0.elapsed_time(ev1) * 1e3 / args.n
+            t_draw = events(lambda: draw_detections(im_d, dets_d, cnt_d, ENCODE_CLASSES, conf=0.8))
+            t_coef = events(lambda: ops.jpeg_coefs(im_d, quality, 2))
+            coef = ops.jpeg_coefs(im_d, quality, 2).cpu()
+            scratch = np.empty(ops.jpeg_stream_bound(geom), dtype=np.uint8)
+            nbytes = len(ops.jpeg_entropy_encode(coef, geom, out=scratch))
+            window(lambda: ops.jpeg_entropy_encode(coef, geom, out=scratch), 20, 1)
+            t_huff = [window(lambda: ops.jpeg_entropy_encode(coef, geom, out=scratch), args.n, 1) for _ in range(args.windows)]
+            print("%dx%d 4:2:0 quality %d, %d boxes: draw %.2f us, ycc + fdct %.2f us per image between events (%d launches each, back to "
+                  "back); coefficients %d B over PCIe against %d B of BGR; host Huffman stage %.3f / %.3f ms per image (min / median of %d "
+                  "windows of %d, one thread); file %d B" % (h, w, quality, ndet, t_draw, t_coef, args.n, coef.numel(), h * w * 3,
+                                                              min(t_huff) * 1e3, float(np.median(t_huff)) * 1e3, args.windows, args.n, nbytes))
+            files = args.files
+            if files <= 0:                                       # --files 0: the launches alone (the process to put under a kernel trace)
+                continue
+
+            def device_path():
+                wr = jpeg.JpegWriter(dev, workers=4, depth=8)
+                for i in range(files):
+                    im_d.copy_(base)
+                    draw_detections(im_d, dets_d, cnt_d, ENCODE_CLASSES, conf=0.8)
+                    wr.submit(os.path.join(tmp, "d%04d.jpg" % i), im_d, quality=quality)
+                wr.close()
+
+            def host_path(threads):
+                def one(i):
+                    _pil_annotate(base.cpu().numpy(), dets, os.path.join(tmp, "h%04d.jpg" % i), quality)
+                if threads == 1:
+                    for i in range(files):
+                        one(i)
+                else:
+                    with ThreadPoolExecutor(max_workers=threads) as ex:
+                        list(ex.map(one, range(files)))
+            cases = (("device draw + JpegWriter, 4 workers", device_path), ("D2H + PIL draw + PIL save, 1 thread", lambda: host_path(1)),
+                     ("D2H + PIL draw + PIL save, 4 threads", lambda: host_path(4)))
+            res = {name: [] for name, _ in cases}
+            for _, fn in cases:
+                fn()
+            for _ in range(3):
+                for name, fn in cases:
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    res[name].append(files / (time.perf_counter() - t0))
+            print("  %d files per run, files per second, three alternated repeats:" % files)
+            for name, _ in cases:
+                print("    %-38s: %s" % (name, "  ".join("%.1f" % v for v in res[name])))
+    finally:
+        for f in os.listdir(tmp):
+            os.remove(os.path.join(tmp, f))
+        os.rmdir(tmp)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--encode", action="store_true")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--n", type=int, default=300, help="decodes per timing window / launches per case")
@@ -231,8 +345,10 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=101)
     ap.add_argument("--batch", type=int, nargs="+", default=[1], help="--e2e: same-size images per launch (1 = the detect_bgr loop)")
     args = ap.parse_args(argv)
-    if not (args.host or args.kernels or args.e2e):
-        ap.error("one of --host / --kernels / --e2e")
+    if not (args.host or args.kernels or args.e2e or args.encode):
+        ap.error("one of --host / --kernels / --e2e / --encode")
+    if args.encode:
+        encode_bench(args)
     if args.host:
         host(args)
     if args.kernels:

@@ -218,6 +218,30 @@ int frcnn_coco_match(const double* det_xywh_d, const long long* det_off_d, const
                      const double* area_rng_d, int A, unsigned char* det_matched_d, unsigned char* det_ignored_d,
                      unsigned char* gt_ignored_d, double* iou_out_d, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- proposal recall, per image: replaces the matching loop of imdb.evaluate_recall (lib/datasets/imdb.py:174-201; csrc/recall_math.h
+ * states the rule; additive, FRCNN_ABI_VERSION unchanged) ------------------------------------------------------------------------ */
+/* n_images images in one launch.  Candidates: boxes_d, n_rows rows of box_stride float32 -- 4: x1,y1,x2,y2; 5: the `rois` layout, column
+ * 0 skipped (any other stride: FRCNN_E_ARG).  Image i owns the rows from start_d[i] (int64); count_d[i] (int32, read ON THE DEVICE, so a
+ * forward's num_rois is consumed without a host round trip) of them exist, clamped to [0, max_boxes] and to n_rows, and the first
+ * `limit` count (limit <= 0: all).  A coordinate is (double)(v / scale_d[i]) with the division in float32.  Ground truth: gt_d
+ * [n_gt_total,4] f64 with offsets gt_off_d [n_images+1] int64, already filtered by class, crowd and area.  Outputs: gt_iou_d [n_gt_total]
+ * f64, slot gt_off[i] + j = the IoU of image i's j-th pick (non-increasing in j); ran_out_d [n_images] int32.  IoU as frcnn_bbox_overlaps.
+ * G picks per image (G = its gts): among unused gts and unused candidates each gt's maximum and its FIRST candidate, the FIRST gt of the
+ * largest maximum; record, retire both.  A gt nothing overlaps records 0.0 and retires the first unused candidate.  With fewer candidates
+ * than gts the remaining slots get -1.0 and ran_out_d[i] = 1 (the reference's assertion); an image without candidates writes no slot.
+ * Nothing but the slots [gt_off[0], gt_off[n_images]) and the flags is written; an image whose offsets leave [0, n_gt_total] is skipped.
+ * ws: frcnn_proposal_recall_workspace_bytes(n_images, max_boxes, n_gt_total) bytes (the IoU matrices); smaller: FRCNN_E_ARG, nothing
+ * launched.  frcnn_proposal_recall_host: the same arguments as HOST pointers (no stream), runs without a GPU; it also refuses a negative
+ * count, a start outside the rows and offsets that decrease or leave [0, n_gt_total] with FRCNN_E_ARG. */
+size_t frcnn_proposal_recall_workspace_bytes(int n_images, long long max_boxes, long long n_gt_total);
+int frcnn_proposal_recall(const float* boxes_d, int box_stride, long long n_rows, const long long* start_d, const int* count_d,
+                          const float* scale_d, int n_images, long long max_boxes, int limit, const double* gt_d,
+                          const long long* gt_off_d, long long n_gt_total, double* gt_iou_d, int* ran_out_d, void* ws, size_t ws_bytes,
+                          void* stream);
+int frcnn_proposal_recall_host(const float* boxes, int box_stride, long long n_rows, const long long* start, const int* count,
+                               const float* scale, int n_images, long long max_boxes, int limit, const double* gt,
+                               const long long* gt_off, long long n_gt_total, double* gt_iou, int* ran_out, void* ws, size_t ws_bytes);
+
 /* ---- dense ops (the TF/slim call sites of lib/nets/network.py:323-378, resnet_v1.py:80-125,
  * vgg16.py:26-60, mobilenet_v1.py:114-172) ---------------------------------------------------- */
 /* Implicit-GEMM convolution on the f32 MFMA pipe (v_mfma_f32_32x32x2_f32).

@@ -57,6 +57,9 @@ SIGNATURES = {
     "frcnn_bbox_overlaps": (c_int, [_P, c_int, _P, c_int, _P, _P]),
     "frcnn_coco_match_workspace_bytes": (c_size_t, [c_int, c_longlong, c_longlong, c_longlong]),
     "frcnn_coco_match": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "frcnn_proposal_recall_workspace_bytes": (c_size_t, [c_int, c_longlong, c_longlong]),
+    "frcnn_proposal_recall": (c_int, [_P, c_int, c_longlong, _P, _P, _P, c_int, c_longlong, c_int, _P, _P, c_longlong, _P, _P, _P, c_size_t, _P]),
+    "frcnn_proposal_recall_host": (c_int, [_P, c_int, c_longlong, _P, _P, _P, c_int, c_longlong, c_int, _P, _P, c_longlong, _P, _P, _P, c_size_t]),
     "frcnn_bbox_transform_inv": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "frcnn_clip_boxes": (c_int, [_P, c_int, c_int, c_float, c_float, _P]),
     "frcnn_bbox_transform": (c_int, [_P, _P, c_int, _P, _P]),

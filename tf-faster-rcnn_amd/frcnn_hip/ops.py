@@ -279,6 +279,47 @@ def coco_match(det_xywh, det_off, gt_xywh, gt_area, gt_crowd, gt_off, iou_thrs, 
     return matched, ignored, gt_ignored, iou
 
 
+def proposal_recall(boxes, start, count, scale, gt, gt_off, max_boxes, limit=None, out=None, ran_out=None):
+    """The matching loop of imdb.evaluate_recall for n_images images in one launch (frcnn_proposal_recall, csrc/recall.hip).  DEVICE
+    tensors: boxes f32 [n_rows, 4 | 5] (5: the `rois` layout), start int64 [n_images] (first row of every image), count int32
+    [n_images] (read by the kernel: a forward's num_rois goes in as it is), scale f32 [n_images], gt f64 [n_gt,4], gt_off int64
+    [n_images+1]; max_boxes bounds every count.  limit None or <= 0: every row counts.  -> (gt_iou f64 [n_gt], ran_out int32
+    [n_images]) on the current stream: slot gt_off[i] + j is image i's j-th pick; the slots of an image without candidates keep what
+    `out` held (zeros when it is allocated here)."""
+    _chk(boxes), _chk(start, torch.int64), _chk(count, torch.int32), _chk(scale), _chk(gt, torch.float64), _chk(gt_off, torch.int64)
+    n_images, n_gt, dev = count.numel(), gt.shape[0], boxes.device
+    if boxes.dim() != 2 or start.numel() != n_images or scale.numel() != n_images or gt_off.numel() != n_images + 1 or gt.shape[1:] != (4,):
+        raise ValueError("proposal_recall: inconsistent sizes")
+    out = _zeros((n_gt,), dtype=torch.float64, device=dev) if out is None else _chk(out, torch.float64)
+    ran_out = _empty((n_images,), dtype=torch.int32, device=dev) if ran_out is None else _chk(ran_out, torch.int32)
+    if out.numel() != n_gt or ran_out.numel() != n_images:
+        raise ValueError("proposal_recall: inconsistent sizes")
+    nbytes = lib().frcnn_proposal_recall_workspace_bytes(n_images, int(max_boxes), n_gt)
+    ws = workspace(nbytes, dev, "proposal_recall")
+    call("frcnn_proposal_recall", _ptr(boxes), boxes.shape[1], boxes.shape[0], _ptr(start), _ptr(count), _ptr(scale), n_images, int(max_boxes),
+         0 if limit is None else int(limit), _ptr(gt), _ptr(gt_off), n_gt, _ptr(out), _ptr(ran_out), _ptr(ws), nbytes, _stream())
+    return out, ran_out
+
+
+def proposal_recall_host(boxes, start, count, scale, gt, gt_off, max_boxes, limit=None):
+    """frcnn_proposal_recall_host: the same on HOST numpy arrays, no GPU needed -> (gt_iou f64 [n_gt] zero-filled, ran_out int32)."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+    start, gt_off = np.ascontiguousarray(start, dtype=np.int64), np.ascontiguousarray(gt_off, dtype=np.int64)
+    count, scale = np.ascontiguousarray(count, dtype=np.int32), np.ascontiguousarray(scale, dtype=np.float32)
+    gt = np.ascontiguousarray(gt, dtype=np.float64).reshape(-1, 4)
+    n_images, n_gt = count.size, gt.shape[0]
+    if boxes.ndim != 2 or start.size != n_images or scale.size != n_images or gt_off.size != n_images + 1:
+        raise ValueError("proposal_recall_host: inconsistent sizes")
+    out, ran_out = np.zeros(n_gt, dtype=np.float64), np.zeros(n_images, dtype=np.int32)
+    nbytes = lib().frcnn_proposal_recall_workspace_bytes(n_images, int(max_boxes), n_gt)
+    ws = np.empty(nbytes, dtype=np.uint8)
+    check(lib().frcnn_proposal_recall_host(boxes.ctypes.data, boxes.shape[1], boxes.shape[0], start.ctypes.data, count.ctypes.data,
+                                           scale.ctypes.data, n_images, int(max_boxes), 0 if limit is None else int(limit), gt.ctypes.data,
+                                           gt_off.ctypes.data, n_gt, out.ctypes.data, ran_out.ctypes.data, ws.ctypes.data, nbytes),
+          "frcnn_proposal_recall_host")
+    return out, ran_out
+
+
 def bbox_transform_inv(boxes, deltas, out=None):
     """lib/model/bbox_transform.py:35-65 on device: boxes [N,4], deltas [N,4k] -> [N,4k]."""
     _chk(boxes), _chk(deltas)

@@ -1,6 +1,8 @@
-"""datasets.imdb -- the image-database base class of the reference (lib/datasets/imdb.py:20-124, 258-260): name, classes, image index,
-the lazily built roidb behind a proposal method, and append_flipped_images.  Proposal-recall evaluation and roidbs built from external
-box lists (selective search, RPN files) are not provided: 'gt' is the only proposal method."""
+"""datasets.imdb -- the image-database base class of the reference (lib/datasets/imdb.py:20-214, 258-260): name, classes, image index,
+the lazily built roidb behind a proposal method, append_flipped_images and evaluate_recall (proposal recall; the matching is
+datasets.recall's, on the device or in its C host statement).  Roidbs built from external box lists (create_roidb_from_box_list,
+merge_roidbs: selective search, RPN files) are not provided, because the network here has no Fast R-CNN mode that would consume such a
+roidb: 'gt' is the only proposal method."""
 import os
 
 import numpy as np
@@ -68,6 +70,13 @@ class imdb(object):
             assert (boxes[:, 2] >= boxes[:, 0]).all()
             self.roidb.append(dict(boxes=boxes, gt_overlaps=src['gt_overlaps'], gt_classes=src['gt_classes'], flipped=True))
         self._image_index = self._image_index * 2
+
+    def evaluate_recall(self, candidate_boxes=None, thresholds=None, area='all', limit=None):
+        """imdb.py:126-214, the reference's signature and result: {'ar', 'recalls', 'thresholds', 'gt_overlaps'}.  candidate_boxes: a list
+        over images of float32 [n,4] (None: the roidb's non-gt rows).  The matching runs on the device when CUDA is available, else in
+        the C host statement (datasets.recall); too few candidates for an image's ground truth raise AssertionError as the reference does."""
+        from datasets import recall
+        return recall.evaluate([self.roidb[i] for i in range(self.num_images)], candidate_boxes, thresholds, area, limit)
 
     def competition_mode(self, on):
         pass

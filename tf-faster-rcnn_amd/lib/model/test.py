@@ -246,6 +246,15 @@ def detect_paths_batched(sess, net, paths, batch, max_per_image=100, thresh=0., 
     just launched; the last read-back is the only wait with nothing behind it.  on_image(i): called once per finished image; on_start(): called once, after
     the pass over the file headers and before the first image is decoded.  max_per_image must be > 0 (checked before any work)."""
     _check_max_per_image(max_per_image)
+    return run_paths_batched(sess, paths, batch, lambda stage, idx, n, ring: _enqueue_batch(sess, net, stage, n, max_per_image, thresh, ring),
+                             _finish_batch, on_image, on_start)
+
+
+def run_paths_batched(sess, paths, batch, enqueue, finish, on_image=None, on_start=None):
+    """The loop of detect_paths_batched for any per-batch work (tools/rpn_recall.py runs the RPN and the recall matcher through it):
+    enqueue(stage [B,h,w,3] uint8 on the device, idx, n_valid, ring) enqueues a batch's launches and ONE non-blocking copy of its record
+    into a pinned buffer taken from `ring` (a _PinnedRing) and returns a pending object without waiting; finish(pending) waits for that
+    record and returns one result per valid image.  -> the results by index into `paths`."""
     sizes = image_sizes(paths)
     plan = plan_batches(sizes, batch)
     order = [i for idx, _ in plan for i in idx]
@@ -260,7 +269,7 @@ def detect_paths_batched(sess, net, paths, batch, max_per_image=100, thresh=0., 
         source = (pil_bgr(paths[i]) for i in order)
 
     def consume(idx, pending):
-        for i, per_class in zip(idx, _finish_batch(pending)):
+        for i, per_class in zip(idx, finish(pending)):
             results[i] = per_class
             if on_image is not None:
                 on_image(i)
@@ -286,7 +295,7 @@ def detect_paths_batched(sess, net, paths, batch, max_per_image=100, thresh=0., 
                 stages.mark(slot)
             for k in range(n, B):
                 stage[k].copy_(stage[n - 1])                 # padding: the last image again, device to device
-            pending = _enqueue_batch(sess, net, stage, n, max_per_image, thresh, records)
+            pending = enqueue(stage, idx, n, records)
             if prev is not None:
                 consume(*prev)
             prev = (idx, pending)

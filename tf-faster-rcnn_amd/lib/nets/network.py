@@ -711,6 +711,58 @@ class Network(object):
             g.launch()
         return self._predictions
 
+    def _build_proposals(self):
+        """_build_network_impl up to the proposals: head, anchors, _region_proposal -> (rois, roi_scores, num_rois int32 [B])"""
+        with self._plan_context(self, False):
+            self._tape = []
+            self._requires_grad = set()
+            self._act_summaries = []
+            self._h2_of, self._f32_missing = {}, set()
+            net_conv = self._image_to_head(False)
+            self._anchor_component()
+            rois = self._region_proposal(net_conv, False)
+        B, per, s = int(self._image.shape[0]), self._rois_per_image, self._sess
+        if self._num_rois is None:                                # TEST.MODE 'top': always RPN_TOP_N rows
+            return rois, s.buf(self._tag + "/top_scores", (per, 1)), torch.full((B,), per, dtype=torch.int32, device=rois.device)
+        return rois, s.buf(self._tag + "/roi_scores", (B * per, 1)), self._num_rois
+
+    def propose_device(self, sess, image_d, im_info, use_graph=True):
+        """The RPN alone on a staged device image (TEST mode): head, anchors and _region_proposal under forward_device's plan context and
+        shape scope, and nothing after them -- no crop, no tail, no classifier.  -> (rois [B*post,5], roi_scores [B*post,1], num_rois
+        int32 [B]) on the device, the very buffers and launches of forward_device, so the same bits for the same image and
+        configuration; a later call or forward_device of the same shape overwrites them in stream order.  TEST.MODE 'nms' is captured
+        into a hipGraph of its own per shape and replayed, under the key ("propose",) + graph_key -- forward_device's graphs and every
+        recorded step keep their keys; the entry names the shape's scope, so it is dropped with the shape's buffers."""
+        assert self._mode == "TEST", "propose_device is a test-time path"
+        self._sess = sess
+        self._image = image_d
+        self._im_info = (float(im_info[0]), float(im_info[1]), float(im_info[2]))
+        sess.prepared.wait_planes()
+        ops.ws_scope = self._tag
+        scope_key = self.graph_key(image_d.shape, self._im_info)
+        key = ("propose",) + scope_key
+        cur = torch.cuda.current_stream(sess.device)
+        with self.shape_scope(sess, image_d.shape, self._im_info):
+            if not use_graph or sess.profile is not None or cfg.TEST.MODE != "nms":
+                sess.flops_last_forward = 0
+                return self._build_proposals()
+            ent = sess.graphs.get(key)
+            if ent is None:
+                with torch.cuda.stream(sess.stream):
+                    sess.stream.wait_stream(cur)
+                    sess.flops_last_forward = 0
+                    out = self._build_proposals()                # warm-up: allocates buffers, packs weights
+                    sess.stream.synchronize()
+                    flops = sess.flops_last_forward
+                    g = ops.Graph().capture(self._build_proposals)
+                    sess.stream.synchronize()
+                ent = sess.graphs[key] = dict(scope=scope_key, graph=g, out=out, flops=flops, per=self._rois_per_image, image=image_d)
+            self._num_rois, sess.flops_last_forward, self._rois_per_image = ent["out"][2], ent["flops"], ent["per"]
+            if ent["image"].data_ptr() != image_d.data_ptr():
+                ent["image"].copy_(image_d, non_blocking=True)   # (as forward_device: the graph reads the image where it was captured)
+            ent["graph"].launch()
+        return ent["out"]
+
     # only useful during testing mode
     def extract_head(self, sess, image):
         self._sess = sess

@@ -423,6 +423,12 @@ int frcnn_winograd_filter_transform_device(const float* w_packed_d, int Cout, in
 int frcnn_winograd_input_transform(const float* x_d, int N, int H, int W, int C, int m, float* v_d, void* stream);
 int frcnn_winograd_output_transform(const float* m_d, int N, int H, int W, int C, int m, const float* bias_d, int act, float* y_d,
                                     void* stream);
+/* F(2x2,3x3) for 64 -> 64 channels in ONE launch (csrc/winograd2_fused.hip; additive, FRCNN_ABI_VERSION unchanged): x [N][H][W][64],
+ * u_planes_d = frcnn_gemm_x3_pack(U [16][64][64]) of the m = 2 filter transform, y = act(conv + bias), act NONE or RELU (else
+ * FRCNN_E_UNSUPPORTED, as for N*H*W >= 2^23).  Bit for bit frcnn_winograd_input_transform -> frcnn_gemm_x3 (G = 16, terms 6) ->
+ * frcnn_winograd_output_transform; V and M never reach memory.  No workspace, no process-wide state. */
+int frcnn_winograd2_conv_x3(const float* x_d, int N, int H, int W, const void* u_planes_d, const float* bias_d, int act, float* y_d,
+                            void* stream);
 /* Winograd for 7x7 maps (the per-RoI crops of block4): each row of 7 outputs = F(4,3) + F(3,3), 11 transform points per
  * dimension, 121 GEMMs of [R x Cin] x [Cin x Cout] (one row per RoI) instead of the 144 of 2x2 F(4x4,3x3) tiles.  Same roles as
  * the frcnn_winograd_* functions: U [121][Cout][Cin] (host float64, or on the device from the packed filter, optionally the

@@ -23,32 +23,14 @@
 // with equal n mod 4 differ in (n >> 2) & 3 -- conflict-free (round 2 used (n >> 1) & 3: two-way conflicts, SQ_LDS_BANK_CONFLICT =
 // half of SQ_LDS_IDX_ACTIVE, profiles/r03_i_pmc_gemm_h2.txt).
 #include "common.h"
-#include "mfma_f32.h"
+#include "x3_mma.h"
 #include <mutex>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 struct GemmX3Params {
   const float* x; const unsigned short* wp; const float* bias; const float* res; float* y;
   int M, N, K, nsteps, mtiles, ntiles, batch, act;
   long long gx, gwp, gy;               // per batch entry: elements of x / bf16 elements of wp (= 3*N*K) / elements of y
 };
-
-// exact split of 8 consecutive k values (two float4) into three bf16x8 operands, every piece rounded to nearest-even
-// (v_cvt_pk_bf16_f32): h = bf16(x), m = bf16(x - h), l = x - h - m.  Both subtractions are exact in f32 and l has at most 8
-// significant bits left, so h + m + l == x; |m| <= 2^-8 |x|, |l| <= 2^-17 |x|, errors of either sign (truncation would bias every
-// product towards zero and is 8x looser: tests/test_x3_math_cpu.py).
-__device__ __forceinline__ void x3_split8(const float4 a, const float4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const __bf16 hq = (__bf16)v[q];
-    const float r = v[q] - (float)hq;
-    const __bf16 mq = (__bf16)r;
-    const float s = r - (float)mq;
-    h[q] = hq; m[q] = mq; l[q] = (__bf16)s;
-  }
-}
 
 template <int BM, int BN, int WM, int WN, int TERMS = 6>   // TERMS = 9: also am*wl, al*wm, al*wl -> every product exact
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_waves_per_eu(2))) void k_gemm_x3(const GemmX3Params p) {
@@ -156,19 +138,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) __attribute__((amdgpu_w
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acs[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acs[i][j], 0, 0, 0);
-          acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], acs[i][j], 0, 0, 0);
-          acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], acs[i][j], 0, 0, 0);
-          acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], acs[i][j], 0, 0, 0);
-          if (TERMS == 9) {
-            acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bl[j], acs[i][j], 0, 0, 0);
-            acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bm[j], acs[i][j], 0, 0, 0);
-            acs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bl[j], acs[i][j], 0, 0, 0);
-          }
-        }
+        for (int j = 0; j < TN; ++j)
+          x3_mma16<TERMS>(ah[i], am[i], al[i], bh[j], bm[j], bl[j], acc[i][j], acs[i][j]);       // csrc/x3_mma.h
     }
     advance_k();
   };

@@ -97,6 +97,7 @@ SIGNATURES = {
     "frcnn_winograd_filter_transform_device": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "frcnn_winograd_input_transform": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "frcnn_winograd_output_transform": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    "frcnn_winograd2_conv_x3": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "frcnn_winograd7_filter_transform": (c_int, [_P, c_int, c_int, _P, _P]),
     "frcnn_winograd7_filter_transform_device": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "frcnn_winograd7_input_transform": (c_int, [_P, c_int, c_int, _P, _P]),

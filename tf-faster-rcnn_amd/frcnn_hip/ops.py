@@ -856,6 +856,18 @@ def winograd_output_transform(mm, bias, act, out, m=2):
     return out
 
 
+def winograd2_conv_x3(x, planes, bias, act, out):
+    """out = act(conv3x3(x, stride 1, SAME) + bias) for x, out [N,H,W,64] as F(2x2,3x3) in one launch (frcnn_winograd2_conv_x3);
+    planes = gemm_x3_pack(U [16,64,64]) of the m = 2 filter transform.  Bit for bit winograd_input_transform -> gemm_x3 ->
+    winograd_output_transform."""
+    N, H, W, C = x.shape
+    if C != 64 or tuple(out.shape) != (N, H, W, 64) or planes.numel() * planes.element_size() != 16 * 3 * 64 * 64 * 2:
+        check(-3, "frcnn_winograd2_conv_x3")            # FRCNN_E_UNSUPPORTED: the entry takes no channel count, so it is refused here
+    _chk(x), _chk(out)
+    call("frcnn_winograd2_conv_x3", _ptr(x), N, H, W, _ptr(planes), _ptr(bias), int(act), _ptr(out), _stream())
+    return out
+
+
 def winograd_output_transform_masked(mm, mask, out, m, out_planes=None):
     """Training: out = mask > 0 ? A^T M A : 0 (no bias, no activation) as float32 `out` [N,H,W,C] and, with `out_planes` (an H2 of
     [N*H*W, C]), as the operand planes of the next data-gradient GEMM too.  m in (4, 7)."""

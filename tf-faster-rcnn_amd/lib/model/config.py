@@ -111,6 +111,9 @@ __C = AttrDict(
     # PREP_STREAM: the weight-only launches of the data-gradient chain (flipped / transposed filters, their h2 split, Winograd transforms of
     # the gradient filters) are re-run by the solver right after the update, on their own stream beside the next forward pass.
     # X3_TILE_CFG: frcnn_gemm_x3's per-call tile configuration (-1 = by shape; A/B runs).
+    # WINOGRAD_FUSED_F2: TEST mode, the F(2x2,3x3) layers with 64 -> 64 channels whose products run in frcnn_gemm_x3 (block1's conv2) as ONE
+    # launch, frcnn_winograd2_conv_x3 (csrc/winograd2_fused.hip): V and M never reach memory, the result is bit for bit the three launches'.
+    # False: input transform, frcnn_gemm_x3, output transform (A/B runs: bench.py --hip WINOGRAD_FUSED_F2=False; profiles/wino2_fused.txt).
     # Round-3 switches that measured no gain were removed in round 4 (OVERLAP_TAIL_ENTRY, TRAIN_GRAPH, H2_TRAIN_WINO, X3_TERMS = 9): the
     # code is kept as scratch/r04_pruned_switches.patch (git apply -R restores it), the measurements in profiles/r02_c_sweep.txt,
     # r03_ab_c5_streams_graph.txt, r02_r_x3_9terms.txt.
@@ -139,7 +142,7 @@ __C = AttrDict(
     # as it was, the default, so that nothing changes unless it is asked for (--set HIP.TEST_BATCH_IMAGES 8).
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
-             WINOGRAD_7X7=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
+             WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
              GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1))

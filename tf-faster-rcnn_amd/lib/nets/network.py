@@ -235,9 +235,16 @@ class Network(object):
         u, b = sess.winograd_params(scope, bn_eps=bn_eps, m=m)
         G, Cout = u.shape[0], u.shape[1]
         T = ops.winograd_tiles(N, H, W, m)
-        mm = sess.buf(self._tag + "/wino_m", (G, T, Cout))
         out = sess.buf(self._tag + "/" + scope, (N, H, W, Cout))
         flops = 2 * G * T * Cout * Cin
+        if (cfg.HIP.WINOGRAD_FUSED_F2 and m == 2 and Cin == 64 and Cout == 64 and self._mode == "TEST" and self._x3_eligible(T, Cout, Cin, G)
+                and N * H * W < (1 << 23)):
+            # block1's conv2: transforms and products in one launch, the bits of the three launches below (csrc/winograd2_fused.hip)
+            planes = sess.x3_planes(u)
+            sess.mark("conv:x3:" + scope, flops, lambda: ops.winograd2_conv_x3(x, planes, b, act, out),
+                      nbytes=4 * (x.numel() + out.numel()) + 6 * u.numel())
+            return self._wrote(out)
+        mm = sess.buf(self._tag + "/wino_m", (G, T, Cout))
         if self._h2_eligible(T, Cout, Cin, G, scope):
             vp, wp = sess.h2_buf(self._tag + "/wino_v", G * T, Cin), sess.h2_planes(u)
             sess.mark("op:wino_in", 0, lambda: ops.winograd_input_transform_h2(x, vp, m), nbytes=4 * (x.numel() + G * T * Cin))

@@ -184,6 +184,30 @@ int frcnn_detect_post_batched(const float* cls_prob_d, const float* bbox_pred_d,
                               float score_thresh, int max_per_image, float* out_dets_d, int* out_count_d, int max_out,
                               long long out_stride, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Soft-NMS (Bodla et al. 2017; csrc/softnms_math.h states the rule; additive, FRCNN_ABI_VERSION unchanged) ------------------- */
+/* Per class, on n candidates with their rows r: pick the largest current score (ties: the lower r; the order of the NMS sort key), stop
+ * once it is < min_score, emit (box, current score, r), multiply every other unselected score by w(IoU with the pick) in float32, repeat.
+ * method 1 (linear): w = 1 - ov where `rule` would have suppressed (CPU: (double)ov >= nms_thresh; GPU: ov > (float)nms_thresh), else 1.
+ * method 2 (Gaussian): w = (float)E(-(double)ov^2 / sigma), E an exponential written out in IEEE double arithmetic (host and device
+ * return the same bits; within 1 float32 ulp of exp).  IoU as in frcnn_nms.  The emission order is the output order; a candidate that is
+ * never emitted is dropped.  FRCNN_E_ARG, nothing launched: method outside {1, 2}, a rule outside {CPU, GPU}, sigma <= 0 or NaN, a NaN
+ * min_score, a null pointer; FRCNN_E_UNSUPPORTED: k or R above 1024.
+ *   frcnn_detect_post_soft_batched: frcnn_detect_post_batched with the per-class stage replaced (one wave per (class, image), the class
+ *       in registers); staging, workspace layout, the max_per_image cut -- now on the DECAYED scores -- and the records are unchanged.
+ *   frcnn_soft_nms: one class, dets_d [k,5] = x1,y1,x2,y2,score -> out_dets_d [k,5] (emitted rows, decayed scores; the rest 0),
+ *       out_index_d [k] (their input rows; the rest -1), *out_count_d.  k <= 1024.
+ *   frcnn_soft_nms_host: the same arguments as HOST pointers (no stream), runs without a GPU; bit for bit the device's result. */
+size_t frcnn_detect_post_soft_batched_workspace_bytes(int B, int R, int C);
+int frcnn_detect_post_soft_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d, const int* num_rois_d,
+                                   int B, int R, int C, double im_scale, int im_h, int im_w, double nms_thresh, int rule,
+                                   float score_thresh, int max_per_image, int method, double sigma, float min_score,
+                                   float* out_dets_d, int* out_count_d, int max_out, long long out_stride, void* ws, size_t ws_bytes,
+                                   void* stream);
+int frcnn_soft_nms(const float* dets_d /*[k,5]*/, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
+                   float* out_dets_d /*[k,5]*/, int* out_index_d /*[k]*/, int* out_count_d, void* stream);
+int frcnn_soft_nms_host(const float* dets /*[k,5]*/, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
+                        float* out_dets /*[k,5]*/, int* out_index /*[k]*/, int* out_count);
+
 /* The box stage of im_detect alone (lib/model/test.py:95-102): pred_boxes [R,4C] = clip(decode(rois/scale,
  * bbox_pred)) for every class, for callers that want the reference's (scores, pred_boxes) pair. */
 int frcnn_im_detect_boxes(const float* rois_d, const float* bbox_pred_d, int R, int C, double im_scale,

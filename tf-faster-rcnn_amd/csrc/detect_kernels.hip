@@ -6,6 +6,7 @@
 // compiled with -ffp-contract=off so every f32 op keeps its own rounding, as in the reference's
 // numpy / Cython code (citations relative to /root/reference/lib).
 #include "common.h"
+#include "softnms_math.h"
 
 // ------------------------------------------------------------------------------------------------
 // anchors  (layer_utils/generate_anchors.py:41-105, layer_utils/snippets.py:14-30)
@@ -1470,4 +1471,229 @@ extern "C" int frcnn_detect_post(const float* cls_prob_d, const float* bbox_pred
   return frcnn_detect_post_batched(cls_prob_d, bbox_pred_d, rois_d, num_rois_d, 1, R, C, im_scale, im_h, im_w, nms_thresh,
                                    FRCNN_NMS_RULE_CPU, score_thresh, max_per_image, out_dets_d, out_count_d, max_out, 0, ws, ws_bytes,
                                    stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Soft-NMS (csrc/softnms_math.h states the rule): per-class suppression that decays a neighbour's score instead of deleting it.
+// There is no bitmask to precompute: a class is a chain of up to R dependent select-then-decay steps, so ONE wave runs it with the
+// class resident in registers -- candidate r sits in lane r % 64, slot r / 64 (PL slots a lane, PL * 64 >= R, PL <= 16): box, area and
+// current score, 6 VGPRs a slot, plus one bit of a per-lane `live` word.  A step: the lane-local best key was already found while the
+// previous step decayed; the wave maximum of its score half and then of its index half (DPP all-reduce inside each row of 16, four
+// readlanes) names the winner, whose lane is r % 64, so its box comes by readlane; lane 0 stores the row; every lane decays its live
+// slots and finds its next local best in the same pass.  No LDS and no barrier anywhere.  Sixteen waves with a barrier per step would
+// spend the step on the barrier pair; the price of one wave is that the Gaussian weight's float64 polynomial (about 40 FP64
+// operations and one FP64 division a candidate) is paid PL times in sequence.  Assumed, not measured, when this was written: about
+// 150 cycles for the two reductions and the broadcast plus about 40 cycles a slot for the linear weight (IoU with its division), i.e.
+// "a few hundred cycles" a step at R = 300.  MEASURED (profiles/soft_nms.txt, 2.4 GHz assumed): 1 400 cycles a step at 2 slots, 2 700
+// (linear) / 4 500 (Gaussian) at the 5 slots of R = 300, 7 000 / 12 500 at 16 -- ten times the estimate.  Presumably a lone wave pays the
+// whole latency of every dependent VALU operation (the IEEE division alone is a chain of ten of them a slot) with nothing else to issue
+// meanwhile.  At 300 rois that is +0.10 ms (linear) / +0.21 ms (Gaussian) on the 0.055 ms of the hard stage for 8 images -- under 2 % of
+// the 8-image step -- but 0.25 ms of the 3.2 ms a one-by-one test_net image takes (309 -> 287 images/s, ResNet-50).
+// The staging is k_perclass_nms's: the r < num_rois && s > score_thresh filter, rois / im_scale, decode_box, the clip, bbox_pred NULL.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 wave_max_u32(u32 v) {       // all 64 lanes active
+  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
+  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
+  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));   // row_half_mirror
+  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));   // row_mirror: every lane holds its row's maximum
+  const u32 a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+  const u32 c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+  return max(max(a, b), max(c, d));
+}
+__device__ __forceinline__ float readlane_f32(float v, int lane_uniform) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_uniform));
+}
+
+// the loop of softnms_math.h on one wave; emit(pos, box, score, r) is called by every lane with uniform arguments -> the count
+template <int PL, int METHOD, typename Emit>
+__device__ __forceinline__ int soft_nms_wave(float4 (&box)[PL], float (&sc)[PL], u32 live, float thr, int rule, double sigma,
+                                             float min_score, Emit emit) {
+  const u32 lane = threadIdx.x;
+  float ar[PL];
+  u32 bhi = 0, blo = 0;                                 // the lane's best live key; 0 = none (no finite score maps to 0)
+  float4 bb = make_float4(0, 0, 0, 0);
+  float ba = 0.0f;
+#pragma unroll
+  for (int i = 0; i < PL; ++i) {
+    ar[i] = softnms_area(box[i].x, box[i].y, box[i].z, box[i].w);
+    const u32 hi = softnms_sortable(sc[i]);
+    if (((live >> i) & 1u) && hi > bhi) {               // slots ascend in r: `>` keeps the lower r of equal scores
+      bhi = hi, blo = ~(lane + 64u * i), bb = box[i], ba = ar[i];
+    }
+  }
+  int m = 0;
+  for (;;) {
+    const u32 whi = wave_max_u32(bhi);
+    if (whi == 0) break;                                // nothing left
+    const float wscore = softnms_unsortable(whi);
+    if (wscore < min_score) break;
+    const u32 wr = ~wave_max_u32(bhi == whi ? blo : 0u);
+    const int wl = __builtin_amdgcn_readfirstlane((int)(wr & 63u));
+    const float4 wb = make_float4(readlane_f32(bb.x, wl), readlane_f32(bb.y, wl), readlane_f32(bb.z, wl), readlane_f32(bb.w, wl));
+    const float wa = readlane_f32(ba, wl);
+    emit(m, wb, wscore, wr);
+    ++m;
+    bhi = 0, blo = 0;
+#pragma unroll
+    for (int i = 0; i < PL; ++i) {
+      const u32 r = lane + 64u * i, bit = 1u << i;
+      if (r == wr) live &= ~bit;
+      if (live & bit) {
+        const float ov = softnms_iou(wb.x, wb.y, wb.z, wb.w, wa, box[i].x, box[i].y, box[i].z, box[i].w, ar[i]);
+        const float w = METHOD == SOFTNMS_LINEAR ? softnms_weight_linear(ov, thr, rule) : softnms_weight_gaussian(ov, sigma);
+        sc[i] = sc[i] * w;
+        const u32 hi = softnms_sortable(sc[i]);
+        if (hi > bhi) bhi = hi, blo = ~r, bb = box[i], ba = ar[i];
+      }
+    }
+  }
+  return m;
+}
+
+template <int PL, int METHOD>
+__global__ __launch_bounds__(64) void k_perclass_soft_nms(const float* __restrict__ prob_all, const float* __restrict__ bbox_pred_all,
+                                                          const float* __restrict__ rois_all, const int* __restrict__ num_rois,
+                                                          int R, int C, double im_scale, float hi_x, float hi_y, float thr, int rule,
+                                                          double sigma, float min_score, float score_thresh,
+                                                          float* __restrict__ cls_dets_all, int* __restrict__ cls_count_all) {
+  const int j = blockIdx.x + 1;                         // class; 0 is background (test.py:162)
+  const int img = blockIdx.y, nfg = C - 1;
+  const float* prob = prob_all + (size_t)img * R * C;
+  const float* bbox_pred = bbox_pred_all + (size_t)img * R * 4 * C;
+  const float* rois = rois_all + (size_t)img * R * 5;
+  float* out = cls_dets_all + ((size_t)img * nfg + blockIdx.x) * (size_t)R * 5;
+  const int lane = threadIdx.x;
+  const int nr = num_rois ? min(num_rois[img], R) : R;
+  float4 box[PL];
+  float sc[PL];
+  u32 live = 0;
+#pragma unroll
+  for (int i = 0; i < PL; ++i) {
+    const int r = lane + 64 * i;
+    float4 b = make_float4(0, 0, 0, 0);
+    float s = 0.0f;
+    if (r < R) {
+      s = prob[(size_t)r * C + j];
+      if ((r < nr) && (s > score_thresh)) {                                                // test.py:163
+        const float* ro = rois + 5 * (size_t)r;
+        const float4 bx = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
+                                      (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));  // test.py:95
+        b = bx;                                                                            // TEST.BBOX_REG False: test.py:103-105
+        if (bbox_pred_all) {
+          const float4 d = *(const float4*)(bbox_pred + (size_t)r * 4 * C + 4 * j);
+          b = decode_box(bx, d);                                                           // test.py:101
+          b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);                                    // test.py:67-77
+          b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
+        }
+        live |= 1u << i;
+      }
+    }
+    box[i] = b;
+    sc[i] = s;
+  }
+  const int n = soft_nms_wave<PL, METHOD>(box, sc, live, thr, rule, sigma, min_score, [&](int pos, float4 b, float s, u32) {
+    if (lane == 0) {                                    // pos < the class's candidates <= R
+      float* o = out + 5 * (size_t)pos;
+      o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = s;
+    }
+  });
+  if (lane == 0) cls_count_all[(size_t)img * nfg + blockIdx.x] = n;
+}
+
+// one class given as dets [k,5]: the emitted rows and their input rows in order, the rest 0 / -1, and the count
+template <int PL, int METHOD>
+__global__ __launch_bounds__(64) void k_soft_nms(const float* __restrict__ dets, int k, float thr, int rule, double sigma, float min_score,
+                                                 float* __restrict__ out_dets, int* __restrict__ out_index, int* __restrict__ out_count) {
+  const int lane = threadIdx.x;
+  float4 box[PL];
+  float sc[PL];
+  u32 live = 0;
+#pragma unroll
+  for (int i = 0; i < PL; ++i) {
+    const int r = lane + 64 * i;
+    float4 b = make_float4(0, 0, 0, 0);
+    float s = 0.0f;
+    if (r < k) {
+      const float* d = dets + 5 * (size_t)r;
+      b = make_float4(d[0], d[1], d[2], d[3]);
+      s = d[4];
+      live |= 1u << i;
+    }
+    box[i] = b;
+    sc[i] = s;
+  }
+  const int n = soft_nms_wave<PL, METHOD>(box, sc, live, thr, rule, sigma, min_score, [&](int pos, float4 b, float s, u32 r) {
+    if (lane == 0) {                                    // pos < k
+      float* o = out_dets + 5 * (size_t)pos;
+      o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = s;
+      out_index[pos] = (int)r;
+    }
+  });
+  for (int p = n + lane; p < k; p += 64) {
+    float* o = out_dets + 5 * (size_t)p;
+    o[0] = o[1] = o[2] = o[3] = o[4] = 0.0f;
+    out_index[p] = -1;
+  }
+  if (lane == 0) *out_count = n;
+}
+
+// slots a lane: 2 (n <= 128), 5 (<= 320: the 300 rois of test time), 8 (<= 512), 16 (<= 1024)
+static int soft_slots(int n) { return n <= 128 ? 2 : n <= 320 ? 5 : n <= 512 ? 8 : 16; }
+#define SOFT_PICK(KERN, pl, method)                                                                                        \
+  ((method) == SOFTNMS_LINEAR ? ((pl) == 2 ? KERN<2, 1> : (pl) == 5 ? KERN<5, 1> : (pl) == 8 ? KERN<8, 1> : KERN<16, 1>)    \
+                              : ((pl) == 2 ? KERN<2, 2> : (pl) == 5 ? KERN<5, 2> : (pl) == 8 ? KERN<8, 2> : KERN<16, 2>))
+
+extern "C" size_t frcnn_detect_post_soft_batched_workspace_bytes(int B, int R, int C) {
+  return frcnn_detect_post_batched_workspace_bytes(B, R, C);
+}
+
+extern "C" int frcnn_detect_post_soft_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
+                                              const int* num_rois_d, int B, int R, int C, double im_scale, int im_h, int im_w,
+                                              double nms_thresh, int rule, float score_thresh, int max_per_image, int method,
+                                              double sigma, float min_score, float* out_dets_d, int* out_count_d, int max_out,
+                                              long long out_stride, void* ws, size_t ws_bytes, void* stream) {
+  if (!cls_prob_d || !rois_d || !out_dets_d || !out_count_d || !ws) return FRCNN_E_ARG;          // bbox_pred_d NULL: TEST.BBOX_REG False
+  if (B <= 0 || R <= 0 || C < 2 || max_out <= 0 || !(im_scale > 0) || !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
+  if (out_stride == 0) out_stride = (long long)max_out * 6;
+  if (out_stride < (long long)max_out * 6) return FRCNN_E_ARG;
+  if (R > PC_MAXR) return FRCNN_E_UNSUPPORTED;
+  if (frcnn_detect_post_batched_workspace_bytes(B, R, C) > ws_bytes) return FRCNN_E_WS;
+  const int nfg = C - 1;
+  char* p = (char*)ws;
+  float* cls_dets = (float*)p;
+  p += align_up((size_t)B * nfg * R * 5 * sizeof(float), 256);
+  int* cls_count = (int*)p;
+  hipStream_t st = (hipStream_t)stream;
+  const int pl = soft_slots(R);
+  auto kern = SOFT_PICK(k_perclass_soft_nms, pl, method);
+  hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(64), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale,
+                     (float)(im_w - 1), (float)(im_h - 1), softnms_thresh_f32(nms_thresh, rule), rule, sigma, min_score, score_thresh,
+                     cls_dets, cls_count);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_final_select, dim3(B), dim3(1024), 0, st, cls_dets, cls_count, nfg, R, max_per_image, out_dets_d,
+                     out_count_d, max_out, out_stride);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_soft_nms(const float* dets_d, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
+                              float* out_dets_d, int* out_index_d, int* out_count_d, void* stream) {
+  if (k < 0 || !dets_d || !out_dets_d || !out_index_d || !out_count_d || !softnms_args_ok(rule, method, sigma, min_score))
+    return FRCNN_E_ARG;
+  if (k > SOFTNMS_MAX) return FRCNN_E_UNSUPPORTED;
+  auto kern = SOFT_PICK(k_soft_nms, soft_slots(k), method);
+  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, (hipStream_t)stream, dets_d, k, softnms_thresh_f32(nms_thresh, rule), rule, sigma,
+                     min_score, out_dets_d, out_index_d, out_count_d);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_soft_nms_host(const float* dets, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
+                                   float* out_dets, int* out_index, int* out_count) {
+  if (k < 0 || !dets || !out_dets || !out_index || !out_count || !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
+  if (k > SOFTNMS_MAX) return FRCNN_E_UNSUPPORTED;
+  float cur[SOFTNMS_MAX];
+  uint64_t key[SOFTNMS_MAX];
+  *out_count = softnms_host(dets, k, softnms_thresh_f32(nms_thresh, rule), rule, method, sigma, min_score, cur, key, out_dets, out_index);
+  return FRCNN_OK;
 }

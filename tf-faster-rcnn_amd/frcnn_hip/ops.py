@@ -436,10 +436,15 @@ def crop_and_resize_bias_act(feat, rois, feat_stride, pool, bias, act, out=None)
 
 
 def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_thresh=0.3, score_thresh=0.0,
-                max_per_image=100, max_out=None, out=None, count=None, batch=1, rule=NMS_RULE_CPU):
+                max_per_image=100, max_out=None, out=None, count=None, batch=1, rule=NMS_RULE_CPU, soft=0, sigma=0.5, min_score=0.001):
     """lib/model/test.py:95-102 + :162-180 on device.  batch = 1: (dets [max_out,6], count [1]).  batch = B: cls_prob
     [B*R,C] (R rows per image), num_rois [B] -> (dets [B,max_out,6], count [B]), one launch pair for all images.
-    bbox_pred = None: cfg.TEST.BBOX_REG False (the rois themselves, un-regressed and un-clipped, test.py:103-105)."""
+    bbox_pred = None: cfg.TEST.BBOX_REG False (the rois themselves, un-regressed and un-clipped, test.py:103-105).
+    soft = 0: hard per-class NMS (exactly the call it always made).  soft = 1 (linear) / 2 (Gaussian with `sigma`): Soft-NMS
+    (frcnn_detect_post_soft_batched, csrc/softnms_math.h) -- a class's neighbours keep a decayed score, rows whose score falls below
+    `min_score` are dropped, and the max_per_image cut sees the decayed scores."""
+    if soft not in (0, 1, 2):
+        raise ValueError("detect_post: soft must be 0 (hard), 1 (linear) or 2 (Gaussian), got %r" % (soft,))
     _chk(cls_prob), _chk(rois)
     if bbox_pred is not None:
         _chk(bbox_pred)
@@ -458,10 +463,44 @@ def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_t
     out_stride = out.stride(0) if out.dim() == 3 else 0
     nb = lib().frcnn_detect_post_batched_workspace_bytes(B, R, C)
     ws = workspace(nb, dev, "detect_post")
+    if soft:
+        call("frcnn_detect_post_soft_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
+             int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), int(soft), float(sigma),
+             float(min_score), _ptr(out), _ptr(count), int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
+        return out, count
     call("frcnn_detect_post_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
          int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), _ptr(out), _ptr(count),
          int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
     return out, count
+
+
+SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2}
+
+
+def soft_nms(dets, nms_thresh=0.3, rule=NMS_RULE_CPU, method=1, sigma=0.5, min_score=0.001):
+    """Soft-NMS of one class on the device (frcnn_soft_nms): dets f32 [k,5] = x1,y1,x2,y2,score, k <= 1024 -> (out [k,5]: the emitted
+    rows in emission order with their decayed scores, the rest 0; index int32 [k]: their input rows, the rest -1; count int32 [1])."""
+    _chk(dets)
+    if dets.dim() != 2 or dets.shape[1] != 5:
+        raise ValueError("soft_nms: dets must be [k,5]")
+    k, dev = dets.shape[0], dets.device
+    out = _empty((max(k, 1), 5), dtype=torch.float32, device=dev)
+    index = _empty((max(k, 1),), dtype=torch.int32, device=dev)
+    count = _zeros((1,), dtype=torch.int32, device=dev)
+    call("frcnn_soft_nms", _ptr(dets if k else out), k, float(nms_thresh), int(rule), int(method), float(sigma), float(min_score), _ptr(out),
+         _ptr(index), _ptr(count), _stream())
+    return out[:k], index[:k], count
+
+
+def soft_nms_host(dets, nms_thresh=0.3, rule=NMS_RULE_CPU, method=1, sigma=0.5, min_score=0.001):
+    """frcnn_soft_nms_host: the same on a HOST numpy array, no GPU needed -> (out f32 [n,5], index int32 [n]) of the n emitted rows."""
+    dets = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 5)
+    k = dets.shape[0]
+    out, index, count = np.zeros((max(k, 1), 5), dtype=np.float32), np.full(max(k, 1), -1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    check(lib().frcnn_soft_nms_host((dets if k else out).ctypes.data, k, float(nms_thresh), int(rule), int(method), float(sigma),
+                                    float(min_score), out.ctypes.data, index.ctypes.data, count.ctypes.data), "frcnn_soft_nms_host")
+    n = int(count[0])
+    return out[:n], index[:n]
 
 
 def im_detect_boxes(rois, bbox_pred, im_scale, im_h, im_w, num_classes=None):

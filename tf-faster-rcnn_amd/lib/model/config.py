@@ -140,12 +140,19 @@ __C = AttrDict(
     # has been enqueued).  all_boxes is the one-by-one loop's, array for array.  A run without a limit per image (max_per_image <= 0) keeps
     # the one-by-one loop: the batched one reads back a fixed-size record per image.  Measurements: profiles/test_net_batched.txt; 1 = the loop
     # as it was, the default, so that nothing changes unless it is asked for (--set HIP.TEST_BATCH_IMAGES 8).
+    # SOFT_NMS: the per-class suppression of Network.detect_device (hence test_net, coco_net, demo, the batched imdb loop): 0 = the hard
+    # greedy rule of TEST.NMS, the default and exactly the launches it always made; 1 = linear, 2 = Gaussian Soft-NMS (Bodla et al. 2017;
+    # csrc/softnms_math.h, frcnn_detect_post_soft_batched): a neighbour's score is multiplied by 1 - IoU where the hard rule would have
+    # deleted it (1) or by exp(-IoU^2 / SOFT_NMS_SIGMA) (2); a box whose score falls below SOFT_NMS_MIN_SCORE is dropped, and the
+    # max_per_image cut sees the decayed scores.  Read at every call (detect_post runs outside the captured graph).  RPN proposal NMS,
+    # TEST.MODE 'top', TRAIN mode, model.test.apply_nms and reval --nms keep the hard rule.  Cost: profiles/soft_nms.txt.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
-             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1))
+             GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1,
+             SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001))
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))
 cfg = __C
 

@@ -620,6 +620,13 @@ class Network(object):
         bad = ["%s = %r (only %r is implemented)" % (k, v, want) for k, v, want in fixed if v != want]
         if float(t.RPN_POSITIVE_WEIGHT) >= 0 and not (0.0 < float(t.RPN_POSITIVE_WEIGHT) < 1.0):
             bad.append("TRAIN.RPN_POSITIVE_WEIGHT = %r (the reference asserts 0 < p < 1, anchor_target_layer.py:103-104)" % (t.RPN_POSITIVE_WEIGHT,))
+        h = cfg.HIP
+        if h.SOFT_NMS not in (0, 1, 2):
+            bad.append("HIP.SOFT_NMS = %r (0 = hard NMS, 1 = linear, 2 = Gaussian)" % (h.SOFT_NMS,))
+        if not float(h.SOFT_NMS_SIGMA) > 0:
+            bad.append("HIP.SOFT_NMS_SIGMA = %r (must be > 0)" % (h.SOFT_NMS_SIGMA,))
+        if not float(h.SOFT_NMS_MIN_SCORE) >= 0:
+            bad.append("HIP.SOFT_NMS_MIN_SCORE = %r (must be >= 0)" % (h.SOFT_NMS_MIN_SCORE,))
         if bad:
             raise NotImplementedError("unsupported configuration for the HIP path: " + "; ".join(bad))
 
@@ -1138,4 +1145,5 @@ class Network(object):
             return sess.mark("op:detect_post", 0, lambda: ops.detect_post(
                 p["cls_prob"], p["bbox_pred"] if cfg.TEST.BBOX_REG else None, p["rois"], self._num_rois, float(im_info[2]), int(im_shape[0]), int(im_shape[1]),
                 float(cfg.TEST.NMS), float(thresh), int(max_per_image), max_out=max_out, out=out, count=count, batch=B,
-                rule=self._nms_rule()), nbytes=B * R * 20 * C)
+                rule=self._nms_rule(), soft=int(cfg.HIP.SOFT_NMS), sigma=float(cfg.HIP.SOFT_NMS_SIGMA),
+                min_score=float(cfg.HIP.SOFT_NMS_MIN_SCORE)), nbytes=B * R * 20 * C)

@@ -17,6 +17,10 @@ Matching the reference's demo (tools/demo.py:89-100, CONF_THRESH 0.8, NMS_THRESH
   * it runs NMS per class and THEN keeps score >= CONF_THRESH; here the threshold comes first (detect_device's `thresh`, the float32 just
     below --conf, so that `score > thresh` is `score >= conf`).  The kept set is the same: greedy NMS visits boxes by descending score and a
     box is only ever suppressed by a higher-scored one, so the boxes below the threshold never decide the fate of one above it.
+
+`--soft-nms linear|gaussian` (with `--sigma`) sets cfg.HIP.SOFT_NMS for the run: a neighbour keeps a decayed score instead of being deleted
+(csrc/softnms_math.h).  A box is likewise only ever decayed by a higher-scored one; rows whose DECAYED score falls below --conf stay in the
+record and are skipped by the drawing kernel and the JSON, which both test score >= conf.
 """
 import argparse
 import json
@@ -35,6 +39,7 @@ NETS = ("vgg16", "res101", "res50", "res152", "mobile")
 DATASETS = {'pascal_voc': ('voc_2007_trainval',), 'pascal_voc_0712': ('voc_2007_trainval+voc_2012_trainval',)}
 IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png", ".bmp")
 MAX_PER_IMAGE = 0                    # detect_device's "no limit": a record of R * (num_classes - 1) rows
+SOFT_NMS = {"linear": 1, "gaussian": 2}
 
 
 def parse_args(argv):
@@ -49,6 +54,9 @@ def parse_args(argv):
     ap.add_argument('--out', default='demo_out', help='directory of the annotated JPEGs')
     ap.add_argument('--conf', type=float, default=0.8, help='keep detections with score >= this')
     ap.add_argument('--nms', type=float, default=0.3, help='NMS overlap threshold (cfg.TEST.NMS)')
+    ap.add_argument('--soft-nms', dest='soft_nms', choices=sorted(SOFT_NMS), default=None,
+                    help='Soft-NMS instead of hard per-class NMS (cfg.HIP.SOFT_NMS): neighbours keep a decayed score')
+    ap.add_argument('--sigma', type=float, default=None, help='the Gaussian Soft-NMS width (cfg.HIP.SOFT_NMS_SIGMA)')
     ap.add_argument('--quality', type=int, default=90, help='JPEG quality of the output')
     ap.add_argument('--json', dest='json_path', default=None, help='also write the kept detections of every image to this file')
     ap.add_argument('--cfg', dest='cfg_file', default=None, help='optional config file')
@@ -144,7 +152,14 @@ def main(argv=None, network=None):
     if args.set_cfgs:
         cfg_from_list(args.set_cfgs)
     saved = (cfg.TEST.HAS_RPN, cfg.TEST.NMS)
+    saved_soft = (cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA)
     cfg.TEST.HAS_RPN, cfg.TEST.NMS = True, float(args.nms)                 # demo.py:114; NMS_THRESH
+    if args.soft_nms is not None:
+        cfg.HIP.SOFT_NMS = SOFT_NMS[args.soft_nms]
+    if args.sigma is not None:
+        if not args.sigma > 0:
+            raise SystemExit("--sigma must be > 0")
+        cfg.HIP.SOFT_NMS_SIGMA = float(args.sigma)
     try:
         sess, net = load_network(args) if network is None else network
         paths = image_paths(args)
@@ -155,6 +170,7 @@ def main(argv=None, network=None):
         print('%d annotated images in %s' % (len(results), args.out))
     finally:
         cfg.TEST.HAS_RPN, cfg.TEST.NMS = saved
+        cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA = saved_soft
     return 0
 
 

@@ -208,6 +208,42 @@ int frcnn_soft_nms(const float* dets_d /*[k,5]*/, int k, double nms_thresh, int 
 int frcnn_soft_nms_host(const float* dets /*[k,5]*/, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
                         float* out_dets /*[k,5]*/, int* out_index /*[k]*/, int* out_count);
 
+/* ---- Box voting and the horizontal-flip ensemble (csrc/boxvote_math.h states both rules; additive, FRCNN_ABI_VERSION unchanged) --- */
+/* Voting, per class and image: every kept detection d (the rows the per-class stage emitted) takes the score-weighted mean of the
+ * candidates c (the rows that ENTERED the stage: decoded, clipped box, ORIGINAL score, ascending row) with (double)IoU_f32(d, c) >=
+ * vote_thresh: W = sum (double)s_c, X_k = sum (double)s_c * (double)box_c[k], sequential IEEE double sums in ascending candidate row,
+ * box_k = (float)(X_k / W); where W is not > 0 the box stays.  Score, class, order and the max_per_image cut do not change.  IoU as in
+ * frcnn_nms.  FRCNN_E_ARG, nothing launched: vote_thresh outside (0, 1] or NaN, a null pointer, a negative count, what the per-class
+ * stage refuses; FRCNN_E_UNSUPPORTED: R, m or n above 1024.
+ *   frcnn_detect_post_vote_batched: frcnn_detect_post_soft_batched's arguments plus vote_thresh; method 0 = the hard stage of
+ *       frcnn_detect_post_batched (sigma, min_score ignored), 1 / 2 = Soft-NMS; then k_perclass_vote (one workgroup per (class, image),
+ *       the candidates re-staged in LDS), then the same final selection.  Workspace: frcnn_detect_post_batched's.
+ *   frcnn_box_vote: one class, kept_d [m,5] and cands_d [n,5] = x1,y1,x2,y2,score -> out_d [m,5] (a buffer of its own).
+ *   frcnn_box_vote_host: the same arguments as HOST pointers (no stream), runs without a GPU; bit for bit the device's result.
+ * Flip ensemble: B images as 2B views, slot 2b as seen and slot 2b+1 mirrored.
+ *   frcnn_mirror_views (csrc/preproc.hip): prepared input in_d [B,OH,OW,c] -> out_d [2B,OH,OW,c]; slot 2b a copy, slot 2b+1 with columns
+ *       x <-> OW-1-x.  The buffers must not overlap.
+ *   frcnn_merge_flip_views: cls_prob_d [2B*R,C], bbox_pred_d [2B*R,4C] (may be NULL, out_pred_d is then not written), rois_d [2B*R,5],
+ *       num_rois_d [2B] (NULL: R rows a slot; read on the device, no synchronisation) -> B images of 2R rows: rows [0,n0) view 0 unchanged,
+ *       rows [n0,n0+n1) view 1 with x1' = (im_w_scaled-1) - x2, x2' = (im_w_scaled-1) - x1 (float32) and dx of EVERY class negated, the rest
+ *       zero; out_num_d [b] = n0 + n1.  im_w_scaled = im_info[1], the width of the prepared image.
+ *   frcnn_merge_flip_views_host: the same arguments as HOST pointers (no stream). */
+size_t frcnn_detect_post_vote_batched_workspace_bytes(int B, int R, int C);
+int frcnn_detect_post_vote_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d, const int* num_rois_d,
+                                   int B, int R, int C, double im_scale, int im_h, int im_w, double nms_thresh, int rule,
+                                   float score_thresh, int max_per_image, int method, double sigma, float min_score, double vote_thresh,
+                                   float* out_dets_d, int* out_count_d, int max_out, long long out_stride, void* ws, size_t ws_bytes,
+                                   void* stream);
+int frcnn_box_vote(const float* kept_d /*[m,5]*/, int m, const float* cands_d /*[n,5]*/, int n, double vote_thresh,
+                   float* out_d /*[m,5]*/, void* stream);
+int frcnn_box_vote_host(const float* kept /*[m,5]*/, int m, const float* cands /*[n,5]*/, int n, double vote_thresh, float* out /*[m,5]*/);
+int frcnn_mirror_views(const float* in_d, int B, int OH, int OW, int c, float* out_d, void* stream);
+int frcnn_merge_flip_views(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d, const int* num_rois_d, int B, int R,
+                           int C, float im_w_scaled, float* out_prob_d, float* out_pred_d, float* out_rois_d, int* out_num_d,
+                           void* stream);
+int frcnn_merge_flip_views_host(const float* cls_prob, const float* bbox_pred, const float* rois, const int* num_rois, int B, int R, int C,
+                                float im_w_scaled, float* out_prob, float* out_pred, float* out_rois, int* out_num);
+
 /* The box stage of im_detect alone (lib/model/test.py:95-102): pred_boxes [R,4C] = clip(decode(rois/scale,
  * bbox_pred)) for every class, for callers that want the reference's (scores, pred_boxes) pair. */
 int frcnn_im_detect_boxes(const float* rois_d, const float* bbox_pred_d, int R, int C, double im_scale,

@@ -7,6 +7,7 @@
 // numpy / Cython code (citations relative to /root/reference/lib).
 #include "common.h"
 #include "softnms_math.h"
+#include "boxvote_math.h"
 
 // ------------------------------------------------------------------------------------------------
 // anchors  (layer_utils/generate_anchors.py:41-105, layer_utils/snippets.py:14-30)
@@ -1695,5 +1696,227 @@ extern "C" int frcnn_soft_nms_host(const float* dets, int k, double nms_thresh, 
   float cur[SOFTNMS_MAX];
   uint64_t key[SOFTNMS_MAX];
   *out_count = softnms_host(dets, k, softnms_thresh_f32(nms_thresh, rule), rule, method, sigma, min_score, cur, key, out_dets, out_index);
+  return FRCNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Bounding-box voting and the merge of two flip views (csrc/boxvote_math.h states both rules).
+// k_perclass_vote runs between the per-class stage (hard or Soft-NMS) and k_final_select: one workgroup per (foreground class, image)
+// re-stages the class's candidates into LDS BY ROW -- k_perclass_nms's filter, rois / im_scale, decode_box and clip, hence its bits; box
+// 16 B + original score 4 B a row, 20 KB at 1024 rows, plus one validity bit a row from a wave ballot -- and then thread t owns the kept
+// detections t, t + 256, ... of cls_dets: it walks the rows in ascending order, every lane of a wave reading the SAME LDS address (a
+// broadcast, no bank conflict), skips the rows that are no candidates (their bit is wave-uniform: no divergence), accumulates the voters in
+// double and overwrites its four coordinates in place.  The trip count is R for every thread.  256 threads: the hard stage keeps a few
+// dozen rows a class, Soft-NMS at min_score 0 up to R -- four waves, one a SIMD, cover 1024 kept rows in four rounds, and the double
+// sums are five additions and four products a VOTER against some thirty float32 operations and a division a CANDIDATE, so the float64
+// rate of the VALU is not what bounds it.  No global atomics, nothing allocated: legal on a capturing stream like its neighbours.
+// ------------------------------------------------------------------------------------------------
+#define VOTE_THREADS 256
+
+struct VoteLds {
+  float4 box[BOXVOTE_MAX];
+  float score[BOXVOTE_MAX];
+  u64 valid[BOXVOTE_MAX / 64];
+};
+
+// rows [0, nrows) of `c` are staged (nrows <= BOXVOTE_MAX); kept [m,5] -> out [m,5] (may be the same rows: a thread reads its row first)
+__device__ __forceinline__ void vote_rows(const VoteLds& c, int nrows, const float* kept, int m, double vote_thresh, float* out) {
+  const int words = (nrows + 63) >> 6;
+  for (int base = 0; base < m; base += VOTE_THREADS) {
+    const int d = base + (int)threadIdx.x;
+    const bool mine = d < m;
+    float a[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (mine)
+      for (int k = 0; k < 5; ++k) a[k] = kept[5 * (size_t)d + k];
+    const float aa = boxvote_area(a[0], a[1], a[2], a[3]);
+    BoxVoteAcc acc;
+    boxvote_clear(acc);
+    for (int w = 0; w < words; ++w) {
+      u64 bits = c.valid[w];
+      while (bits) {
+        const int r = w * 64 + (int)__builtin_ctzll(bits);
+        bits &= bits - 1;
+        const float4 b = c.box[r];
+        boxvote_see(acc, a[0], a[1], a[2], a[3], aa, b.x, b.y, b.z, b.w, c.score[r], vote_thresh);
+      }
+    }
+    if (mine) {
+      boxvote_finish(acc, a);
+      for (int k = 0; k < 5; ++k) out[5 * (size_t)d + k] = a[k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(VOTE_THREADS) void k_perclass_vote(const float* __restrict__ prob_all, const float* __restrict__ bbox_pred_all,
+                                                                const float* __restrict__ rois_all, const int* __restrict__ num_rois,
+                                                                int R, int C, double im_scale, float hi_x, float hi_y, float score_thresh,
+                                                                double vote_thresh, float* __restrict__ cls_dets_all,
+                                                                const int* __restrict__ cls_count_all) {
+  __shared__ VoteLds c;
+  const int j = blockIdx.x + 1;                         // class; 0 is background (test.py:162)
+  const int img = blockIdx.y, nfg = C - 1;
+  const float* prob = prob_all + (size_t)img * R * C;
+  const float* bbox_pred = bbox_pred_all + (size_t)img * R * 4 * C;
+  const float* rois = rois_all + (size_t)img * R * 5;
+  float* dets = cls_dets_all + ((size_t)img * nfg + blockIdx.x) * (size_t)R * 5;
+  const int tid = threadIdx.x;
+  const int nr = num_rois ? min(num_rois[img], R) : R;
+  for (int base = 0; base < R; base += VOTE_THREADS) {  // R <= 1024 and base a multiple of 256 below it: r <= 1023
+    const int r = base + tid;
+    bool valid = false;
+    float4 b = make_float4(0, 0, 0, 0);
+    float s = 0.0f;
+    if (r < R) {
+      s = prob[(size_t)r * C + j];
+      valid = (r < nr) && (s > score_thresh);                                              // test.py:163
+      if (valid) {
+        const float* ro = rois + 5 * (size_t)r;
+        const float4 box = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
+                                       (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));  // test.py:95
+        b = box;                                                                           // TEST.BBOX_REG False: test.py:103-105
+        if (bbox_pred_all) {
+          const float4 dl = *(const float4*)(bbox_pred + (size_t)r * 4 * C + 4 * j);
+          b = decode_box(box, dl);                                                         // test.py:101
+          b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);                                    // test.py:67-77
+          b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
+        }
+      }
+    }
+    const u64 bal = __ballot(valid);                    // the wave's 64 rows are one word: r >> 6 is uniform in the wave
+    c.box[r] = b;
+    c.score[r] = s;
+    if ((tid & 63) == 0) c.valid[r >> 6] = bal;
+  }
+  __syncthreads();
+  const int m = min(cls_count_all[(size_t)img * nfg + blockIdx.x], R);
+  vote_rows(c, R, dets, m, vote_thresh, dets);
+}
+
+// one class: kept [m,5] and cands [n,5] in global memory -> out [m,5]
+__global__ __launch_bounds__(VOTE_THREADS) void k_box_vote(const float* __restrict__ kept, int m, const float* __restrict__ cands, int n,
+                                                           double vote_thresh, float* __restrict__ out) {
+  __shared__ VoteLds c;
+  const int tid = threadIdx.x;
+  for (int base = 0; base < n; base += VOTE_THREADS) {  // n <= 1024: r <= 1023
+    const int r = base + tid;
+    const bool valid = r < n;
+    float4 b = make_float4(0, 0, 0, 0);
+    float s = 0.0f;
+    if (valid) {
+      const float* d = cands + 5 * (size_t)r;
+      b = make_float4(d[0], d[1], d[2], d[3]);
+      s = d[4];
+    }
+    const u64 bal = __ballot(valid);
+    c.box[r] = b;
+    c.score[r] = s;
+    if ((tid & 63) == 0) c.valid[r >> 6] = bal;
+  }
+  __syncthreads();
+  vote_rows(c, n, kept, m, vote_thresh, out);
+}
+
+#define MERGE_THREADS 128
+// one workgroup per output row (2R rows an image): the row's 5C + 5 values, see boxvote_math.h; the counts are read on the device
+__global__ __launch_bounds__(MERGE_THREADS) void k_merge_flip_views(const float* __restrict__ cls_prob, const float* __restrict__ bbox_pred,
+                                                                    const float* __restrict__ rois, const int* __restrict__ num_rois,
+                                                                    int R, int C, float wm1, float* __restrict__ out_prob,
+                                                                    float* __restrict__ out_pred, float* __restrict__ out_rois,
+                                                                    int* __restrict__ out_num) {
+  const int rp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int n0 = num_rois ? boxvote_clamp_count(num_rois[2 * b], R) : R, n1 = num_rois ? boxvote_clamp_count(num_rois[2 * b + 1], R) : R;
+  int view, row;
+  boxvote_merge_source(rp, n0, n1, &view, &row);
+  const size_t src = (size_t)(2 * b + (view > 0 ? 1 : 0)) * R + row, dst = (size_t)b * 2 * R + rp;
+  for (int j = tid; j < C; j += MERGE_THREADS) out_prob[dst * C + j] = boxvote_merge_prob(cls_prob + src * C, view, j);
+  if (bbox_pred)
+    for (int k = tid; k < 4 * C; k += MERGE_THREADS) out_pred[dst * 4 * C + k] = boxvote_merge_delta(bbox_pred + src * 4 * C, view, k);
+  if (tid < 5) out_rois[dst * 5 + tid] = boxvote_merge_roi(rois + src * 5, view, tid, wm1);
+  if (rp == 0 && tid == 0) out_num[b] = n0 + n1;
+}
+
+extern "C" size_t frcnn_detect_post_vote_batched_workspace_bytes(int B, int R, int C) {
+  return frcnn_detect_post_batched_workspace_bytes(B, R, C);
+}
+
+extern "C" int frcnn_detect_post_vote_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
+                                              const int* num_rois_d, int B, int R, int C, double im_scale, int im_h, int im_w,
+                                              double nms_thresh, int rule, float score_thresh, int max_per_image, int method,
+                                              double sigma, float min_score, double vote_thresh, float* out_dets_d, int* out_count_d,
+                                              int max_out, long long out_stride, void* ws, size_t ws_bytes, void* stream) {
+  if (!cls_prob_d || !rois_d || !out_dets_d || !out_count_d || !ws) return FRCNN_E_ARG;          // bbox_pred_d NULL: TEST.BBOX_REG False
+  if (B <= 0 || R <= 0 || C < 2 || max_out <= 0 || !(im_scale > 0) || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
+  if (method != 0 && method != SOFTNMS_LINEAR && method != SOFTNMS_GAUSSIAN) return FRCNN_E_ARG;
+  if (method == 0 ? !rule_ok(rule) : !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
+  if (out_stride == 0) out_stride = (long long)max_out * 6;
+  if (out_stride < (long long)max_out * 6) return FRCNN_E_ARG;
+  if (R > PC_MAXR) return FRCNN_E_UNSUPPORTED;
+  if (frcnn_detect_post_batched_workspace_bytes(B, R, C) > ws_bytes) return FRCNN_E_WS;
+  const int nfg = C - 1;
+  char* p = (char*)ws;
+  float* cls_dets = (float*)p;
+  p += align_up((size_t)B * nfg * R * 5 * sizeof(float), 256);
+  int* cls_count = (int*)p;
+  hipStream_t st = (hipStream_t)stream;
+  const float hi_x = (float)(im_w - 1), hi_y = (float)(im_h - 1);
+  if (method == 0) {
+    const size_t lds = perclass_lds_bytes(R);
+    auto kern = rule == NMS_RULE_GPU ? k_perclass_nms<NMS_RULE_GPU> : k_perclass_nms<NMS_RULE_CPU>;
+    if (lds > 48 * 1024)      // (as frcnn_detect_post_batched)
+      HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(PC_THREADS), lds, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale, hi_x,
+                       hi_y, rule_threshold(nms_thresh, rule), score_thresh, cls_dets, cls_count);
+  } else {
+    auto kern = SOFT_PICK(k_perclass_soft_nms, soft_slots(R), method);
+    hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(64), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale, hi_x, hi_y,
+                       softnms_thresh_f32(nms_thresh, rule), rule, sigma, min_score, score_thresh, cls_dets, cls_count);
+  }
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_perclass_vote, dim3(nfg, B), dim3(VOTE_THREADS), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C,
+                     im_scale, hi_x, hi_y, score_thresh, vote_thresh, cls_dets, (const int*)cls_count);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_final_select, dim3(B), dim3(1024), 0, st, cls_dets, cls_count, nfg, R, max_per_image, out_dets_d,
+                     out_count_d, max_out, out_stride);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_box_vote(const float* kept_d, int m, const float* cands_d, int n, double vote_thresh, float* out_d, void* stream) {
+  if (m < 0 || n < 0 || !kept_d || !cands_d || !out_d || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
+  if (m > BOXVOTE_MAX || n > BOXVOTE_MAX) return FRCNN_E_UNSUPPORTED;
+  if (m == 0) return FRCNN_OK;
+  hipLaunchKernelGGL(k_box_vote, dim3(1), dim3(VOTE_THREADS), 0, (hipStream_t)stream, kept_d, m, cands_d, n, vote_thresh, out_d);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_box_vote_host(const float* kept, int m, const float* cands, int n, double vote_thresh, float* out) {
+  if (m < 0 || n < 0 || !kept || !cands || !out || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
+  if (m > BOXVOTE_MAX || n > BOXVOTE_MAX) return FRCNN_E_UNSUPPORTED;
+  boxvote_host(kept, m, cands, n, vote_thresh, out);
+  return FRCNN_OK;
+}
+
+static bool merge_args_ok(const void* cls_prob, const void* rois, int B, int R, int C, float im_w_scaled, const void* out_prob,
+                          const void* bbox_pred, const void* out_pred, const void* out_rois, const void* out_num) {
+  return cls_prob && rois && out_prob && out_rois && out_num && (!bbox_pred || out_pred) && B > 0 && R > 0 && C >= 2 && im_w_scaled > 0;
+}
+
+extern "C" int frcnn_merge_flip_views(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d, const int* num_rois_d,
+                                      int B, int R, int C, float im_w_scaled, float* out_prob_d, float* out_pred_d, float* out_rois_d,
+                                      int* out_num_d, void* stream) {
+  if (!merge_args_ok(cls_prob_d, rois_d, B, R, C, im_w_scaled, out_prob_d, bbox_pred_d, out_pred_d, out_rois_d, out_num_d)) return FRCNN_E_ARG;
+  if (B > 65535) return FRCNN_E_ARG;
+  hipLaunchKernelGGL(k_merge_flip_views, dim3(2 * R, B), dim3(MERGE_THREADS), 0, (hipStream_t)stream, cls_prob_d, bbox_pred_d, rois_d,
+                     num_rois_d, R, C, im_w_scaled - 1.0f, out_prob_d, out_pred_d, out_rois_d, out_num_d);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+extern "C" int frcnn_merge_flip_views_host(const float* cls_prob, const float* bbox_pred, const float* rois, const int* num_rois, int B,
+                                           int R, int C, float im_w_scaled, float* out_prob, float* out_pred, float* out_rois,
+                                           int* out_num) {
+  if (!merge_args_ok(cls_prob, rois, B, R, C, im_w_scaled, out_prob, bbox_pred, out_pred, out_rois, out_num)) return FRCNN_E_ARG;
+  boxvote_merge_host(cls_prob, bbox_pred, rois, num_rois, B, R, C, im_w_scaled, out_prob, out_pred, out_rois, out_num);
   return FRCNN_OK;
 }

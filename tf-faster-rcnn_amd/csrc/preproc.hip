@@ -143,6 +143,29 @@ extern "C" int frcnn_prep_image_batched(const void* src_d, int src_is_float, int
   return FRCNN_OK;
 }
 
+// The two views of the test-time flip ensemble (cfg.HIP.TEST_FLIP): slot 2b = prepared image b, slot 2b+1 = its columns x <-> OW-1-x.
+// One thread per source pixel writes both; an exact permutation of the PREPARED image (not a second resize of the mirrored source).
+__global__ void k_mirror_views(const float* __restrict__ in, int OH, int OW, int c, float* __restrict__ out) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+  if (x >= OW) return;
+  const float* s = in + (((size_t)b * OH + y) * OW + x) * c;
+  float* o0 = out + (((size_t)(2 * b) * OH + y) * OW + x) * c;
+  float* o1 = out + (((size_t)(2 * b + 1) * OH + y) * OW + (OW - 1 - x)) * c;
+  for (int k = 0; k < c; ++k) {
+    const float v = s[k];
+    o0[k] = v;
+    o1[k] = v;
+  }
+}
+
+// in_d [B][OH][OW][c] -> out_d [2B][OH][OW][c] (B <= 65535, OH <= 65535: the grid's limits; c >= 1); the buffers must not overlap
+extern "C" int frcnn_mirror_views(const float* in_d, int B, int OH, int OW, int c, float* out_d, void* stream) {
+  if (!in_d || !out_d || B <= 0 || OH <= 0 || OW <= 0 || c <= 0 || B > 65535 || OH > 65535) return FRCNN_E_ARG;
+  hipLaunchKernelGGL(k_mirror_views, dim3((OW + 255) / 256, OH, B), dim3(256), 0, (hipStream_t)stream, in_d, OH, OW, c, out_d);
+  LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
 // minibatch.py:44-46: gt_boxes[:, 0:4] = boxes (uint16) * im_scale (Python float) -> float64 product, rounded once into the float32 blob;
 // gt_boxes[:, 4] = gt_classes (int32).  One thread per row.
 __global__ void k_fill_gt(const unsigned short* __restrict__ boxes, const int* __restrict__ classes, int G, double im_scale,

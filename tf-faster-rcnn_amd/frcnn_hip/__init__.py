@@ -55,6 +55,14 @@ SIGNATURES = {
                                                c_int, c_double, c_float, _P, _P, c_int, c_longlong, _P, c_size_t, _P]),
     "frcnn_soft_nms": (c_int, [_P, c_int, c_double, c_int, c_int, c_double, c_float, _P, _P, _P, _P]),
     "frcnn_soft_nms_host": (c_int, [_P, c_int, c_double, c_int, c_int, c_double, c_float, _P, _P, _P]),
+    "frcnn_detect_post_vote_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "frcnn_detect_post_vote_batched": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_float, c_int,
+                                               c_int, c_double, c_float, c_double, _P, _P, c_int, c_longlong, _P, c_size_t, _P]),
+    "frcnn_box_vote": (c_int, [_P, c_int, _P, c_int, c_double, _P, _P]),
+    "frcnn_box_vote_host": (c_int, [_P, c_int, _P, c_int, c_double, _P]),
+    "frcnn_mirror_views": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "frcnn_merge_flip_views": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
+    "frcnn_merge_flip_views_host": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
     "frcnn_detect_post_workspace_bytes": (c_size_t, [c_int, c_int]),
     "frcnn_detect_post": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, c_int, c_int, c_double, c_float, c_int, _P, _P,
                                   c_int, _P, c_size_t, _P]),

@@ -436,15 +436,21 @@ def crop_and_resize_bias_act(feat, rois, feat_stride, pool, bias, act, out=None)
 
 
 def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_thresh=0.3, score_thresh=0.0,
-                max_per_image=100, max_out=None, out=None, count=None, batch=1, rule=NMS_RULE_CPU, soft=0, sigma=0.5, min_score=0.001):
+                max_per_image=100, max_out=None, out=None, count=None, batch=1, rule=NMS_RULE_CPU, soft=0, sigma=0.5, min_score=0.001,
+                vote=0.0):
     """lib/model/test.py:95-102 + :162-180 on device.  batch = 1: (dets [max_out,6], count [1]).  batch = B: cls_prob
     [B*R,C] (R rows per image), num_rois [B] -> (dets [B,max_out,6], count [B]), one launch pair for all images.
     bbox_pred = None: cfg.TEST.BBOX_REG False (the rois themselves, un-regressed and un-clipped, test.py:103-105).
     soft = 0: hard per-class NMS (exactly the call it always made).  soft = 1 (linear) / 2 (Gaussian with `sigma`): Soft-NMS
     (frcnn_detect_post_soft_batched, csrc/softnms_math.h) -- a class's neighbours keep a decayed score, rows whose score falls below
-    `min_score` are dropped, and the max_per_image cut sees the decayed scores."""
+    `min_score` are dropped, and the max_per_image cut sees the decayed scores.
+    vote = 0: off (the calls above, untouched).  0 < vote <= 1: bounding-box voting (frcnn_detect_post_vote_batched, csrc/boxvote_math.h)
+    between the per-class stage and the cut -- every kept box becomes the score-weighted mean of the class's candidates whose IoU with it
+    is >= vote; scores, classes and order stay."""
     if soft not in (0, 1, 2):
         raise ValueError("detect_post: soft must be 0 (hard), 1 (linear) or 2 (Gaussian), got %r" % (soft,))
+    if not (vote == 0 or 0.0 < vote <= 1.0):
+        raise ValueError("detect_post: vote must be 0 (off) or a threshold in (0, 1], got %r" % (vote,))
     _chk(cls_prob), _chk(rois)
     if bbox_pred is not None:
         _chk(bbox_pred)
@@ -463,6 +469,11 @@ def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_t
     out_stride = out.stride(0) if out.dim() == 3 else 0
     nb = lib().frcnn_detect_post_batched_workspace_bytes(B, R, C)
     ws = workspace(nb, dev, "detect_post")
+    if vote:
+        call("frcnn_detect_post_vote_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
+             int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), int(soft), float(sigma),
+             float(min_score), float(vote), _ptr(out), _ptr(count), int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
+        return out, count
     if soft:
         call("frcnn_detect_post_soft_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
              int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), int(soft), float(sigma),
@@ -501,6 +512,88 @@ def soft_nms_host(dets, nms_thresh=0.3, rule=NMS_RULE_CPU, method=1, sigma=0.5, 
                                     float(min_score), out.ctypes.data, index.ctypes.data, count.ctypes.data), "frcnn_soft_nms_host")
     n = int(count[0])
     return out[:n], index[:n]
+
+
+def box_vote(kept, cands, vote_thresh=0.8):
+    """Bounding-box voting of one class on the device (frcnn_box_vote, csrc/boxvote_math.h): kept f32 [m,5], cands f32 [n,5] =
+    x1,y1,x2,y2,score, m, n <= 1024 -> out [m,5]: every kept box replaced by the score-weighted mean of the candidates whose IoU with it
+    is >= vote_thresh (sequential double sums in candidate order); scores and order as in `kept`."""
+    _chk(kept), _chk(cands)
+    if kept.dim() != 2 or kept.shape[1] != 5 or cands.dim() != 2 or cands.shape[1] != 5:
+        raise ValueError("box_vote: kept and cands must be [m,5] and [n,5]")
+    m, n, dev = kept.shape[0], cands.shape[0], kept.device
+    out = _empty((max(m, 1), 5), dtype=torch.float32, device=dev)
+    call("frcnn_box_vote", _ptr(kept if m else out), m, _ptr(cands if n else out), n, float(vote_thresh), _ptr(out), _stream())
+    return out[:m]
+
+
+def box_vote_host(kept, cands, vote_thresh=0.8):
+    """frcnn_box_vote_host: the same on HOST numpy arrays, no GPU needed -> out f32 [m,5], the device's bits."""
+    kept = np.ascontiguousarray(kept, dtype=np.float32).reshape(-1, 5)
+    cands = np.ascontiguousarray(cands, dtype=np.float32).reshape(-1, 5)
+    m, n = kept.shape[0], cands.shape[0]
+    out = np.zeros((max(m, 1), 5), dtype=np.float32)
+    check(lib().frcnn_box_vote_host((kept if m else out).ctypes.data, m, (cands if n else out).ctypes.data, n, float(vote_thresh),
+                                    out.ctypes.data), "frcnn_box_vote_host")
+    return out[:m]
+
+
+def mirror_views(image, out=None):
+    """The two views of the test-time flip ensemble (frcnn_mirror_views): prepared input [B,OH,OW,c] -> [2B,OH,OW,c], slot 2b image b as
+    it is, slot 2b+1 its columns mirrored (an exact permutation)."""
+    _chk(image)
+    if image.dim() != 4:
+        raise ValueError("mirror_views: image must be [B,OH,OW,c]")
+    B, OH, OW, c = image.shape
+    out = _empty((2 * B, OH, OW, c), dtype=torch.float32, device=image.device) if out is None else out
+    if tuple(out.shape) != (2 * B, OH, OW, c) or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() == image.data_ptr():
+        raise ValueError("mirror_views: `out` must be a float32 contiguous [2B,OH,OW,c] buffer of its own")
+    call("frcnn_mirror_views", _ptr(image), B, OH, OW, c, _ptr(out), _stream())
+    return out
+
+
+def merge_flip_views(cls_prob, bbox_pred, rois, num_rois, im_w_scaled, batch=1, out=None):
+    """The outputs of the 2B views of mirror_views as B images of 2R rows (frcnn_merge_flip_views): cls_prob [2B*R,C], bbox_pred
+    [2B*R,4C] or None, rois [2B*R,5], num_rois int32 [2B] or None -> (cls_prob [B*2R,C], bbox_pred [B*2R,4C] or None, rois [B*2R,5],
+    num_rois int32 [B]).  Per image: view 0's rows, then view 1's with their x mirrored back about the prepared width im_w_scaled
+    (= im_info[1]) and dx negated, then zeros.  The counts are read on the device.  out = the four result buffers, to reuse them."""
+    _chk(cls_prob), _chk(rois)
+    if bbox_pred is not None:
+        _chk(bbox_pred)
+    B = int(batch)
+    rows, C = cls_prob.shape
+    R = rows // (2 * B)
+    if rows != 2 * B * R or R == 0 or rois.shape[0] != rows or (bbox_pred is not None and tuple(bbox_pred.shape) != (rows, 4 * C)):
+        raise ValueError("merge_flip_views: %d rows do not split into 2 views of %d images" % (rows, B))
+    dev = cls_prob.device
+    if out is None:
+        out = (_empty((rows, C), dtype=torch.float32, device=dev),
+               None if bbox_pred is None else _empty((rows, 4 * C), dtype=torch.float32, device=dev),
+               _empty((rows, 5), dtype=torch.float32, device=dev), _empty((B,), dtype=torch.int32, device=dev))
+    o_prob, o_pred, o_rois, o_num = out
+    call("frcnn_merge_flip_views", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_w_scaled), _ptr(o_prob),
+         _ptr(o_pred if bbox_pred is not None else None), _ptr(o_rois), _ptr(o_num), _stream())
+    return o_prob, (o_pred if bbox_pred is not None else None), o_rois, o_num
+
+
+def merge_flip_views_host(cls_prob, bbox_pred, rois, num_rois, im_w_scaled, batch=1):
+    """frcnn_merge_flip_views_host: merge_flip_views on HOST numpy arrays, no GPU needed."""
+    cls_prob = np.ascontiguousarray(cls_prob, dtype=np.float32)
+    rois = np.ascontiguousarray(rois, dtype=np.float32)
+    bbox_pred = None if bbox_pred is None else np.ascontiguousarray(bbox_pred, dtype=np.float32)
+    num_rois = None if num_rois is None else np.ascontiguousarray(num_rois, dtype=np.int32)
+    B = int(batch)
+    rows, C = cls_prob.shape
+    R = rows // (2 * B)
+    if rows != 2 * B * R or R == 0 or rois.shape != (rows, 5) or (bbox_pred is not None and bbox_pred.shape != (rows, 4 * C)) or \
+            (num_rois is not None and num_rois.shape != (2 * B,)):
+        raise ValueError("merge_flip_views_host: %d rows do not split into 2 views of %d images" % (rows, B))
+    o_prob, o_rois, o_num = np.empty((rows, C), np.float32), np.empty((rows, 5), np.float32), np.empty((B,), np.int32)
+    o_pred = None if bbox_pred is None else np.empty((rows, 4 * C), np.float32)
+    p = lambda a: None if a is None else a.ctypes.data
+    check(lib().frcnn_merge_flip_views_host(p(cls_prob), p(bbox_pred), p(rois), p(num_rois), B, R, C, float(im_w_scaled), p(o_prob),
+                                            p(o_pred), p(o_rois), p(o_num)), "frcnn_merge_flip_views_host")
+    return o_prob, o_pred, o_rois, o_num
 
 
 def im_detect_boxes(rois, bbox_pred, im_scale, im_h, im_w, num_classes=None):

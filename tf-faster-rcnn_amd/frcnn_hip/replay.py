@@ -227,4 +227,5 @@ HOST_ONLY = frozenset(["frcnn_generate_anchors", "frcnn_winograd_filter_transfor
                        "frcnn_graph_launch", "frcnn_graph_destroy", "frcnn_abi_version", "frcnn_build_info", "frcnn_sgd_desc_bytes",
                        "frcnn_conv2d_wgrad_supported", "frcnn_jpeg_info", "frcnn_jpeg_entropy_decode", "frcnn_jpeg_pixels_host", "frcnn_summary_limits",
                        "frcnn_jpeg_quant_tables", "frcnn_jpeg_coefs_host", "frcnn_jpeg_stream_bound", "frcnn_jpeg_entropy_encode",
-                       "frcnn_draw_detections_host", "frcnn_proposal_recall_host", "frcnn_soft_nms_host"])
+                       "frcnn_draw_detections_host", "frcnn_proposal_recall_host", "frcnn_soft_nms_host",
+                       "frcnn_box_vote_host", "frcnn_merge_flip_views_host"])

@@ -146,13 +146,21 @@ __C = AttrDict(
     # deleted it (1) or by exp(-IoU^2 / SOFT_NMS_SIGMA) (2); a box whose score falls below SOFT_NMS_MIN_SCORE is dropped, and the
     # max_per_image cut sees the decayed scores.  Read at every call (detect_post runs outside the captured graph).  RPN proposal NMS,
     # TEST.MODE 'top', TRAIN mode, model.test.apply_nms and reval --nms keep the hard rule.  Cost: profiles/soft_nms.txt.
+    # TEST_FLIP: the horizontal-flip ensemble of Network.detect_device (Detectron's TEST.BBOX_AUG.H_FLIP): False = off, the default and
+    # exactly the launches it always made; True = every prepared image runs together with its mirror (frcnn_mirror_views: B images are one
+    # forward pass of 2B views, a shape and captured graph of its own), the mirror's proposals and deltas are turned back and appended
+    # (frcnn_merge_flip_views) and the post-processing sees B images of 2 * RPN_POST_NMS_TOP_N rows -- at most 1024, so 300 proposals
+    # pass and 1000 are refused, as is TEST.MODE 'top'.  BBOX_VOTE: bounding-box voting (Gidaris & Komodakis 2015; csrc/boxvote_math.h,
+    # frcnn_detect_post_vote_batched) after the per-class stage, hard or Soft-NMS: every kept box becomes the score-weighted mean of the
+    # class's candidates whose IoU with it is >= BBOX_VOTE_THRESH (in (0, 1]); scores, order and the max_per_image cut stay.  All three
+    # are read at every call, like SOFT_NMS, and reach the same callers.  Cost (one more launch; about a doubled forward): profiles/tta.txt.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
              GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1,
-             SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001))
+             SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001, TEST_FLIP=False, BBOX_VOTE=False, BBOX_VOTE_THRESH=0.8))
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))
 cfg = __C
 

@@ -627,8 +627,25 @@ class Network(object):
             bad.append("HIP.SOFT_NMS_SIGMA = %r (must be > 0)" % (h.SOFT_NMS_SIGMA,))
         if not float(h.SOFT_NMS_MIN_SCORE) >= 0:
             bad.append("HIP.SOFT_NMS_MIN_SCORE = %r (must be >= 0)" % (h.SOFT_NMS_MIN_SCORE,))
+        if not 0.0 < float(h.BBOX_VOTE_THRESH) <= 1.0:
+            bad.append("HIP.BBOX_VOTE_THRESH = %r (must be in (0, 1])" % (h.BBOX_VOTE_THRESH,))
+        if h.TEST_FLIP and mode == "TEST":
+            bad += Network._flip_refusals()
         if bad:
             raise NotImplementedError("unsupported configuration for the HIP path: " + "; ".join(bad))
+
+    FLIP_MAX_ROWS = 1024                  # rows per image and class the post-processing holds (frcnn_detect_post_*: R <= 1024)
+
+    @staticmethod
+    def _flip_refusals():
+        """what HIP.TEST_FLIP cannot run with: the merged image has 2 * RPN_POST_NMS_TOP_N rows, refused rather than truncated"""
+        bad = []
+        if cfg.TEST.MODE != "nms":
+            bad.append("HIP.TEST_FLIP with TEST.MODE = %r (the flip ensemble merges the 'nms' proposals of two views)" % (cfg.TEST.MODE,))
+        elif 2 * int(cfg.TEST.RPN_POST_NMS_TOP_N) > Network.FLIP_MAX_ROWS:
+            bad.append("HIP.TEST_FLIP with TEST.RPN_POST_NMS_TOP_N = %d (two views give %d rows per image, the post-processing holds at most %d)"
+                       % (int(cfg.TEST.RPN_POST_NMS_TOP_N), 2 * int(cfg.TEST.RPN_POST_NMS_TOP_N), Network.FLIP_MAX_ROWS))
+        return bad
 
     def create_architecture(self, mode, num_classes, tag=None, anchor_scales=(8, 16, 32), anchor_ratios=(0.5, 1, 2)):
         assert tag is not None
@@ -1130,6 +1147,9 @@ class Network(object):
         """image(s) already in HBM -> final detections in HBM: forward + the whole of lib/model/test.py:95-102,
         162-180 on device.  One image: returns (dets [max_out,6], count [1]).  A batch [B,H,W,4] of same-size images:
         dets [B,max_out,6], count [B] (the dense layers run once for the batch, the per-image stages once per image)."""
+        vote = float(cfg.HIP.BBOX_VOTE_THRESH) if cfg.HIP.BBOX_VOTE else 0.0    # (read per call, like SOFT_NMS: detect_post runs outside the graph)
+        if cfg.HIP.TEST_FLIP:
+            return self._detect_device_flip(sess, image_d, im_info, im_shape, max_per_image, thresh, out, count, vote)
         p = self.forward_device(sess, image_d, im_info)
         ops.ws_scope = self._tag
         B = image_d.shape[0]
@@ -1146,4 +1166,40 @@ class Network(object):
                 p["cls_prob"], p["bbox_pred"] if cfg.TEST.BBOX_REG else None, p["rois"], self._num_rois, float(im_info[2]), int(im_shape[0]), int(im_shape[1]),
                 float(cfg.TEST.NMS), float(thresh), int(max_per_image), max_out=max_out, out=out, count=count, batch=B,
                 rule=self._nms_rule(), soft=int(cfg.HIP.SOFT_NMS), sigma=float(cfg.HIP.SOFT_NMS_SIGMA),
-                min_score=float(cfg.HIP.SOFT_NMS_MIN_SCORE)), nbytes=B * R * 20 * C)
+                min_score=float(cfg.HIP.SOFT_NMS_MIN_SCORE), vote=vote), nbytes=B * R * 20 * C)
+
+    def _detect_device_flip(self, sess, image_d, im_info, im_shape, max_per_image, thresh, out, count, vote):
+        """detect_device under cfg.HIP.TEST_FLIP: the B staged images and their mirrors as ONE forward pass of 2B views (slot 2b as seen,
+        2b+1 mirrored: ops.mirror_views, an exact permutation of the prepared image) -- a shape of its own, hence its own captured graph
+        and buffer scope --, the two views' rows merged per image (ops.merge_flip_views: the mirror's rois turned back about im_info[1], its
+        dx negated) and the usual post-processing on B images of 2R rows.  The same records for the callers: [B,max_out,6] / [B]."""
+        bad = self._flip_refusals()
+        if bad:
+            raise NotImplementedError("unsupported configuration for the HIP path: " + "; ".join(bad))
+        B = int(image_d.shape[0])
+        shape2 = (2 * B,) + tuple(int(v) for v in image_d.shape[1:])
+        with self.shape_scope(sess, shape2, im_info):
+            views = sess.buf(self._tag + "/flip_views", shape2)
+        ops.ws_scope = self._tag
+        ops.mirror_views(image_d, out=views)
+        p = self.forward_device(sess, views, im_info)
+        ops.ws_scope = self._tag
+        R, C = self._rois_per_image, self._num_classes
+        assert self._num_rois is not None and 2 * R <= self.FLIP_MAX_ROWS
+        reg = bool(cfg.TEST.BBOX_REG)
+        max_out = None if out is None else out.shape[-2]
+        with self.shape_scope(sess, shape2, im_info):
+            merged = (sess.buf(self._tag + "/flip_cls_prob", (B * 2 * R, C)), sess.buf(self._tag + "/flip_bbox_pred", (B * 2 * R, 4 * C)) if reg else None,
+                      sess.buf(self._tag + "/flip_rois", (B * 2 * R, 5)), sess.buf(self._tag + "/flip_num_rois", (B,), torch.int32))
+            m_prob, m_pred, m_rois, m_num = sess.mark("op:merge_flip_views", 0, lambda: ops.merge_flip_views(
+                p["cls_prob"], p["bbox_pred"] if reg else None, p["rois"], self._num_rois, float(im_info[1]), batch=B, out=merged),
+                nbytes=2 * B * R * (5 * C + 5) * 8)
+            if B > 1:
+                max_out = (max_per_image + 28) if out is None else max_out
+                out = sess.buf(self._tag + "/dets", (B, max_out, 6)) if out is None else out
+                count = sess.buf(self._tag + "/det_count", (B,), torch.int32) if count is None else count
+            return sess.mark("op:detect_post", 0, lambda: ops.detect_post(
+                m_prob, m_pred, m_rois, m_num, float(im_info[2]), int(im_shape[0]), int(im_shape[1]),
+                float(cfg.TEST.NMS), float(thresh), int(max_per_image), max_out=max_out, out=out, count=count, batch=B,
+                rule=self._nms_rule(), soft=int(cfg.HIP.SOFT_NMS), sigma=float(cfg.HIP.SOFT_NMS_SIGMA),
+                min_score=float(cfg.HIP.SOFT_NMS_MIN_SCORE), vote=vote), nbytes=B * 2 * R * 20 * C)

@@ -21,6 +21,11 @@ Matching the reference's demo (tools/demo.py:89-100, CONF_THRESH 0.8, NMS_THRESH
 `--soft-nms linear|gaussian` (with `--sigma`) sets cfg.HIP.SOFT_NMS for the run: a neighbour keeps a decayed score instead of being deleted
 (csrc/softnms_math.h).  A box is likewise only ever decayed by a higher-scored one; rows whose DECAYED score falls below --conf stay in the
 record and are skipped by the drawing kernel and the JSON, which both test score >= conf.
+
+`--flip` sets cfg.HIP.TEST_FLIP (every image runs together with its mirror, the two views' proposals are merged before the per-class stage;
+about twice the forward pass) and `--vote [THRESH]` sets cfg.HIP.BBOX_VOTE / BBOX_VOTE_THRESH (default 0.8): every kept box becomes the
+score-weighted mean of the class's candidates whose IoU with it is >= THRESH (csrc/boxvote_math.h).  The candidates are the boxes with
+score >= --conf, since the threshold comes first here: a box below it does not vote.
 """
 import argparse
 import json
@@ -57,6 +62,9 @@ def parse_args(argv):
     ap.add_argument('--soft-nms', dest='soft_nms', choices=sorted(SOFT_NMS), default=None,
                     help='Soft-NMS instead of hard per-class NMS (cfg.HIP.SOFT_NMS): neighbours keep a decayed score')
     ap.add_argument('--sigma', type=float, default=None, help='the Gaussian Soft-NMS width (cfg.HIP.SOFT_NMS_SIGMA)')
+    ap.add_argument('--flip', action='store_true', help='horizontal-flip ensemble (cfg.HIP.TEST_FLIP): the image and its mirror in one pass')
+    ap.add_argument('--vote', type=float, nargs='?', const=0.8, default=None, metavar='THRESH',
+                    help='bounding-box voting (cfg.HIP.BBOX_VOTE) with this IoU threshold in (0, 1] (cfg.HIP.BBOX_VOTE_THRESH, 0.8 if omitted)')
     ap.add_argument('--quality', type=int, default=90, help='JPEG quality of the output')
     ap.add_argument('--json', dest='json_path', default=None, help='also write the kept detections of every image to this file')
     ap.add_argument('--cfg', dest='cfg_file', default=None, help='optional config file')
@@ -153,6 +161,7 @@ def main(argv=None, network=None):
         cfg_from_list(args.set_cfgs)
     saved = (cfg.TEST.HAS_RPN, cfg.TEST.NMS)
     saved_soft = (cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA)
+    saved_tta = (cfg.HIP.TEST_FLIP, cfg.HIP.BBOX_VOTE, cfg.HIP.BBOX_VOTE_THRESH)
     cfg.TEST.HAS_RPN, cfg.TEST.NMS = True, float(args.nms)                 # demo.py:114; NMS_THRESH
     if args.soft_nms is not None:
         cfg.HIP.SOFT_NMS = SOFT_NMS[args.soft_nms]
@@ -160,6 +169,12 @@ def main(argv=None, network=None):
         if not args.sigma > 0:
             raise SystemExit("--sigma must be > 0")
         cfg.HIP.SOFT_NMS_SIGMA = float(args.sigma)
+    if args.flip:
+        cfg.HIP.TEST_FLIP = True
+    if args.vote is not None:
+        if not 0.0 < args.vote <= 1.0:
+            raise SystemExit("--vote must be in (0, 1]")
+        cfg.HIP.BBOX_VOTE, cfg.HIP.BBOX_VOTE_THRESH = True, float(args.vote)
     try:
         sess, net = load_network(args) if network is None else network
         paths = image_paths(args)
@@ -171,6 +186,7 @@ def main(argv=None, network=None):
     finally:
         cfg.TEST.HAS_RPN, cfg.TEST.NMS = saved
         cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA = saved_soft
+        cfg.HIP.TEST_FLIP, cfg.HIP.BBOX_VOTE, cfg.HIP.BBOX_VOTE_THRESH = saved_tta
     return 0
 
 

@@ -161,6 +161,23 @@ int frcnn_crop_and_resize_bias_act(const float* feat_d, int N, int H, int W, int
  * per (roi, output row, slab) (rounds 2-4) instead of one per (roi, slab) -- the same bits. */
 int frcnn_detect_set_tuning(int key, int value);
 
+/* ---- RoIAlign (cfg.POOLING_MODE = 'align'): Mask R-CNN / Detectron semantics without the half-pixel shift; the rule is stated once
+ * in csrc/roialign_math.h.  spatial_scale = 1 / feat_stride; `samples` x `samples` bilinear samples per bin (1..4, fixed), averaged;
+ * a sample outside [-1, H] x [-1, W] contributes 0.  All float32, one rounding per operation. -------------------------------------- */
+/* feat_d [N,H,W,C], rois_d [R,5] (image index, x1, y1, x2, y2), out_d [R,pool,pool,C] = act(align(feat) + bias[c]) with bias_d NULL =
+ * no bias and act FRCNN_ACT_NONE / FRCNN_ACT_RELU (the epilogue of the fused tail entry: a 1x1 convolution commutes with the linear
+ * pooling, the bias goes after it).  Rows whose image index is outside [0,N) produce zeros.  One workgroup per (roi, channel slab),
+ * the slab count as for the crop (frcnn_detect_set_tuning key 4).  R == 0 succeeds; C % 4 != 0 or pool * samples > 128:
+ * FRCNN_E_UNSUPPORTED.  The result does not depend on N, on the row's position in rois_d, or on the slab count. */
+int frcnn_roi_align_batched(const float* feat_d, int N, int H, int W, int C, const float* rois_d, int R, float feat_stride, int pool,
+                            int samples, const float* bias_d, int act, float* out_d, void* stream);
+/* The same statement over HOST pointers (no GPU involved): the bit-exact reference of the kernel.  Any C. */
+int frcnn_roi_align_host(const float* feat, int N, int H, int W, int C, const float* rois, int R, float feat_stride, int pool,
+                         int samples, const float* bias, int act, float* out);
+/* counts [R][4] (host): how many of a RoI's (pool*samples)^2 samples are zeroed, clamped to 0, clamped to the last row / column, or
+ * lie on an integer coordinate -- the classification of csrc/roialign_math.h, so that a test can assert which branches its inputs take */
+int frcnn_roi_align_classify_host(int H, int W, const float* rois, int R, float feat_stride, int pool, int samples, long long* counts);
+
 /* ---- test-time post-processing: replaces lib/model/test.py:95-102 (im_detect) and :162-180
  * (test_net per-class NMS + max_per_image cut) ----------------------------------------------- */
 size_t frcnn_detect_post_workspace_bytes(int R, int C);
@@ -683,6 +700,17 @@ int frcnn_crop_and_resize_bwd(const float* dout_d, int H, int W, int C, const fl
                               int pool, float* dfeat_d, void* stream);
 int frcnn_crop_and_resize_bwd_plan(const float* dout_d, int H, int W, int C, const float* rois_d, int R, float feat_stride,
                                    int pool, float* dfeat_d, size_t max_lds_bytes, void* stream);
+/* Gradient of frcnn_roi_align_batched w.r.t. the feature map of ONE image (rois[:,0] is not read): dfeat_d += sum over the samples of
+ * (dout / samples^2) * tap weight.  The deterministic gather of the crop's backward over the R * pool * samples sample rows: each feature
+ * element sums its taps from 0 in (roi, ph, iy, pw, ix, tap) order and the sum is added to dfeat once; no float atomics; the same launch
+ * plan (256 / 128 / 64 channels per workgroup, windowed hit list, W up to ~600) and the same bits under every plan.
+ * _host: the same statement and the same order over HOST pointers. */
+int frcnn_roi_align_bwd(const float* dout_d, int H, int W, int C, const float* rois_d, int R, float feat_stride, int pool, int samples,
+                        float* dfeat_d, void* stream);
+int frcnn_roi_align_bwd_plan(const float* dout_d, int H, int W, int C, const float* rois_d, int R, float feat_stride, int pool,
+                             int samples, float* dfeat_d, size_t max_lds_bytes, void* stream);
+int frcnn_roi_align_bwd_host(const float* dout, int H, int W, int C, const float* rois, int R, float feat_stride, int pool, int samples,
+                             float* dfeat);
 /* tf.train.MomentumOptimizer step on a packed master filter [Cout][K] (+ refresh of the BN-folded copy):
  * g = grad_scale*grad*scale[n] + weight_decay*w ; acc = momentum*acc + g ; w -= lr*acc ; w_folded = w*scale[n].
  * scale_d / w_folded_d may be NULL (biases, fc). */

@@ -1094,6 +1094,8 @@ static int launch_crop(const float* feat_d, int NIMG, int H, int W, int C, const
   return FRCNN_OK;
 }
 
+int frcnn_detect_crop_slabs() { return g_crop_slabs; }      // csrc/roi_align.hip launches on the same slab rule
+
 extern "C" int frcnn_detect_set_tuning(int key, int value) {
   if (key == 4) { g_crop_slabs = value; return FRCNN_OK; }
   if (key == 5) { g_crop_form = value; return FRCNN_OK; }

@@ -47,6 +47,9 @@ SIGNATURES = {
     "frcnn_crop_and_resize_batched": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P, _P]),
     "frcnn_crop_and_resize_bias_act": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_int, _P, c_int, _P, _P]),
     "frcnn_detect_set_tuning": (c_int, [c_int, c_int]),
+    "frcnn_roi_align_batched": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P, c_int, _P, _P]),
+    "frcnn_roi_align_host": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P, c_int, _P]),
+    "frcnn_roi_align_classify_host": (c_int, [c_int, c_int, _P, c_int, c_float, c_int, c_int, _P]),
     "frcnn_detect_post_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "frcnn_detect_post_batched": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_float, c_int,
                                           _P, _P, c_int, c_longlong, _P, c_size_t, _P]),
@@ -177,6 +180,9 @@ SIGNATURES = {
     "frcnn_colsum": (c_int, [_P, c_int, c_int, _P, _P]),
     "frcnn_crop_and_resize_bwd": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, c_int, _P, _P]),
     "frcnn_crop_and_resize_bwd_plan": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, c_int, _P, c_size_t, _P]),
+    "frcnn_roi_align_bwd": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P, _P]),
+    "frcnn_roi_align_bwd_plan": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P, c_size_t, _P]),
+    "frcnn_roi_align_bwd_host": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_float, c_int, c_int, _P]),
     "frcnn_sgd_momentum": (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, c_float, c_float, c_float, c_float, _P]),
     "frcnn_sgd_desc_bytes": (c_size_t, []),
     "frcnn_sgd_momentum_multi": (c_int, [_P, c_int, c_float, c_float, c_float, _P]),

@@ -435,6 +435,68 @@ def crop_and_resize_bias_act(feat, rois, feat_stride, pool, bias, act, out=None)
     return out
 
 
+def roi_align(feat, rois, feat_stride, pool, samples, out=None):
+    """RoIAlign (csrc/roialign_math.h): feat [N,H,W,C] or [H,W,C]; rois [R,5] with rois[:,0] = image index -> [R,pool,pool,C], the mean
+    of samples x samples bilinear samples per bin."""
+    return roi_align_bias_act(feat, rois, feat_stride, pool, samples, None, ACT_NONE, out=out)
+
+
+def roi_align_bias_act(feat, rois, feat_stride, pool, samples, bias, act, out=None):
+    """act(roi_align(feat) + bias): see frcnn_roi_align_batched."""
+    _chk(feat), _chk(rois)
+    H, W, C = feat.shape[-3:]
+    N = feat.shape[0] if feat.dim() == 4 else 1
+    R = rois.shape[0]
+    out = _empty((R, pool, pool, C), dtype=torch.float32, device=feat.device) if out is None else out
+    call("frcnn_roi_align_batched", _ptr(feat), N, H, W, C, _ptr(rois), R, float(feat_stride), int(pool), int(samples), _ptr(bias),
+         int(act), _ptr(out), _stream())
+    return out
+
+
+def _host_f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a if shape is None else a.reshape(shape)
+
+
+def roi_align_host(feat, rois, feat_stride, pool, samples, bias=None, act=ACT_NONE):
+    """frcnn_roi_align_host: the same on HOST numpy arrays, no GPU needed -> f32 [R,pool,pool,C], the device's bits."""
+    feat, rois = _host_f32(feat), _host_f32(rois, (-1, 5))
+    if feat.ndim == 3:
+        feat = feat[None]
+    N, H, W, C = feat.shape
+    R = rois.shape[0]
+    bias = None if bias is None else _host_f32(bias, (C,))
+    out = np.empty((R, pool, pool, C), dtype=np.float32)
+    check(lib().frcnn_roi_align_host(feat.ctypes.data, N, H, W, C, rois.ctypes.data if R else None, R, float(feat_stride), int(pool),
+                                     int(samples), None if bias is None else bias.ctypes.data, int(act), out.ctypes.data if R else None),
+          "frcnn_roi_align_host")
+    return out
+
+
+def roi_align_bwd_host(dout, rois, feat_stride, samples, dfeat):
+    """frcnn_roi_align_bwd_host: dfeat (numpy f32 [H,W,C], contiguous, modified in place) += the gradient of dout [R,P,P,C]."""
+    dout, rois = _host_f32(dout), _host_f32(rois, (-1, 5))
+    if not (isinstance(dfeat, np.ndarray) and dfeat.dtype == np.float32 and dfeat.flags.c_contiguous and dfeat.ndim == 3):
+        raise ValueError("roi_align_bwd_host: dfeat must be a contiguous float32 [H,W,C] array")
+    R, P, _, C = dout.shape
+    H, W = dfeat.shape[0], dfeat.shape[1]
+    if dfeat.shape[2] != C or rois.shape[0] != R:
+        raise ValueError("roi_align_bwd_host: shapes disagree")
+    check(lib().frcnn_roi_align_bwd_host(dout.ctypes.data if R else None, H, W, C, rois.ctypes.data if R else None, R, float(feat_stride),
+                                         int(P), int(samples), dfeat.ctypes.data), "frcnn_roi_align_bwd_host")
+    return dfeat
+
+
+def roi_align_classify_host(H, W, rois, feat_stride, pool, samples):
+    """-> int64 [R,4]: a RoI's zeroed, clamped-low, clamped-high and integer-coordinate samples (the kinds of csrc/roialign_math.h)."""
+    rois = _host_f32(rois, (-1, 5))
+    counts = np.zeros((rois.shape[0], 4), dtype=np.int64)
+    if rois.shape[0]:
+        check(lib().frcnn_roi_align_classify_host(int(H), int(W), rois.ctypes.data, rois.shape[0], float(feat_stride), int(pool), int(samples),
+                                                  counts.ctypes.data), "frcnn_roi_align_classify_host")
+    return counts
+
+
 def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_thresh=0.3, score_thresh=0.0,
                 max_per_image=100, max_out=None, out=None, count=None, batch=1, rule=NMS_RULE_CPU, soft=0, sigma=0.5, min_score=0.001,
                 vote=0.0):
@@ -1514,6 +1576,19 @@ def crop_and_resize_bwd(dout, rois, feat_stride, dfeat, max_lds=0):
         call("frcnn_crop_and_resize_bwd_plan", _ptr(dout), H, W, C, _ptr(rois), R, float(feat_stride), P, _ptr(dfeat), int(max_lds), _stream())
     else:
         call("frcnn_crop_and_resize_bwd", _ptr(dout), H, W, C, _ptr(rois), R, float(feat_stride), P, _ptr(dfeat), _stream())
+    return dfeat
+
+
+def roi_align_bwd(dout, rois, feat_stride, samples, dfeat, max_lds=0):
+    """dfeat += gradient of roi_align w.r.t. the feature map (one image).  max_lds (bytes; tests): the LDS budget of the launch plan."""
+    _chk(dout), _chk(rois), _chk(dfeat)
+    R, P, _, C = dout.shape
+    H, W = dfeat.shape[-3], dfeat.shape[-2]
+    if max_lds:
+        call("frcnn_roi_align_bwd_plan", _ptr(dout), H, W, C, _ptr(rois), R, float(feat_stride), P, int(samples), _ptr(dfeat), int(max_lds),
+             _stream())
+    else:
+        call("frcnn_roi_align_bwd", _ptr(dout), H, W, C, _ptr(rois), R, float(feat_stride), P, int(samples), _ptr(dfeat), _stream())
     return dfeat
 
 

@@ -216,7 +216,7 @@ class Sweep(object):
         self.producer = {}
         if self.fuse:
             for r in self.net._tape:
-                if r["kind"] not in ("mean", "crop", "maxpool", "dropout", "dwconv"):
+                if r["kind"] not in ("mean", "crop", "roi_align", "maxpool", "dropout", "dwconv"):
                     self.producer[r["y"].data_ptr()] = r
         self.masked, self.borrowed, self.emitted = set(), set(), {}
 
@@ -264,7 +264,7 @@ class Sweep(object):
 
     def run(self, seeds):
         self.grads = {t.data_ptr(): g for t, g in seeds}
-        visit = {"mean": self.visit_mean, "crop": self.visit_crop, "maxpool": self.visit_maxpool, "dropout": self.visit_dropout,
+        visit = {"mean": self.visit_mean, "crop": self.visit_crop, "roi_align": self.visit_roi_align, "maxpool": self.visit_maxpool, "dropout": self.visit_dropout,
                  "dwconv": self.visit_dwconv, "conv": self.visit_conv}
         for rec in reversed(self.net._tape):
             visit[rec["kind"]](rec)
@@ -399,6 +399,15 @@ class Sweep(object):
         if not had:
             self.ops.t_zero(gx)
         self.ops.crop_and_resize_bwd(gy.view(rec["y"].shape), rec["rois"], rec["stride"], gx)
+
+    def visit_roi_align(self, rec):
+        gy, feat = self.grads.get(rec["y"].data_ptr()), rec["feat"]
+        if gy is None or feat.data_ptr() not in self.needs:
+            return
+        gx, had = self.accumulate_into(feat, feat.shape, "feat")
+        if not had:
+            self.ops.t_zero(gx)
+        self.ops.roi_align_bwd(gy.view(rec["y"].shape), rec["rois"], rec["stride"], rec["samples"], gx)
 
     def visit_dwconv(self, rec):
         y, x, sc = rec["y"], rec["x"], rec["scope"]

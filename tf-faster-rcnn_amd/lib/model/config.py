@@ -154,13 +154,28 @@ __C = AttrDict(
     # frcnn_detect_post_vote_batched) after the per-class stage, hard or Soft-NMS: every kept box becomes the score-weighted mean of the
     # class's candidates whose IoU with it is >= BBOX_VOTE_THRESH (in (0, 1]); scores, order and the max_per_image cut stay.  All three
     # are read at every call, like SOFT_NMS, and reach the same callers.  Cost (one more launch; about a doubled forward): profiles/tta.txt.
+    # ROI_ALIGN_SAMPLES: the S of POOLING_MODE 'align' (RoIAlign as in Mask R-CNN / Detectron without the half-pixel shift; the rule is
+    # csrc/roialign_math.h): every POOLING_SIZE x POOLING_SIZE bin is the mean of S x S bilinear samples, S in 1..4 and fixed (no adaptive
+    # ceil(roi / P) count).  Only read when POOLING_MODE is 'align'; 'crop' (tf.image.crop_and_resize, the reference's only mode) stays the
+    # default and exactly the launches it always made.  Part of the graph key.  Cost next to the crop: profiles/roi_align.txt.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
              MFMA_H2=True, H2_LAZY_SPLIT=True, H2_MIN_TILES=150, H2_TRAIN_MIN_TILES=320, H2_TRUNK_PLANES=True, H2_TILE_CFG=-1,
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
              GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1,
-             SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001, TEST_FLIP=False, BBOX_VOTE=False, BBOX_VOTE_THRESH=0.8))
+             SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001, TEST_FLIP=False, BBOX_VOTE=False, BBOX_VOTE_THRESH=0.8,
+             ROI_ALIGN_SAMPLES=2))
+
+
+def pooling_description(c=None):
+    """One line for the tools' logs: a snapshot does not record the RoI pooling it was trained with, so every tool prints what it runs."""
+    c = __C if c is None else c
+    if c.POOLING_MODE == 'align':
+        return "RoI pooling: align (RoIAlign, %d x %d samples per bin)" % (c.HIP.ROI_ALIGN_SAMPLES, c.HIP.ROI_ALIGN_SAMPLES)
+    return "RoI pooling: %s" % (c.POOLING_MODE,)
+
+
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))
 cfg = __C
 

@@ -466,7 +466,10 @@ class Network(object):
         fs, P = float(self._feat_stride[0]), cfg.POOLING_SIZE
         self._need_f32(bottom)
         nbytes = 4 * (bottom.numel() + out.numel())
-        if bias is None and act == ACT_NONE:
+        if cfg.POOLING_MODE == "align":              # csrc/roialign_math.h; max_pool does not apply (see _crop_pool)
+            S = int(cfg.HIP.ROI_ALIGN_SAMPLES)
+            self._sess.mark("op:roi_align", 0, lambda: ops.roi_align_bias_act(bottom, rois, fs, P, S, bias, act, out=out), nbytes=nbytes)
+        elif bias is None and act == ACT_NONE:
             self._sess.mark("op:crop_and_resize", 0, lambda: ops.crop_and_resize(bottom, rois, fs, P, max_pool=max_pool, out=out), nbytes=nbytes)
         else:
             self._sess.mark("op:crop_and_resize", 0, lambda: ops.crop_and_resize_bias_act(bottom, rois, fs, P, bias, act, out=out), nbytes=nbytes)
@@ -482,6 +485,15 @@ class Network(object):
         P, C = cfg.POOLING_SIZE, bottom.shape[-1]
         R = rois.shape[0]
         fs = float(self._feat_stride[0])
+        if cfg.POOLING_MODE == "align":
+            # RoIAlign in its standard form for every backbone: POOLING_SIZE x POOLING_SIZE bins of S x S samples, no 14x14 + 2x2 max detour
+            S = int(cfg.HIP.ROI_ALIGN_SAMPLES)
+            out = self._crop_images(bottom, rois, self._sess.buf(self._tag + "/" + name, (R, P, P, C)))
+            if self._mode == "TRAIN":
+                self._tape.append(dict(kind="roi_align", feat=bottom, rois=rois, y=out, stride=fs, samples=S))
+                if bottom.data_ptr() in self._requires_grad:
+                    self._requires_grad.add(out.data_ptr())
+            return out
         if self._mode != "TRAIN":
             return self._crop_images(bottom, rois, self._sess.buf(self._tag + "/" + name, (R, P, P, C)), max_pool=max_pool)
         pre = 2 * P if max_pool else P
@@ -596,8 +608,6 @@ class Network(object):
         self._anchor_component()
         fused = self._fuse_tail_entry and not is_training and hasattr(self, "_fused_tail_entry")      # a method of resnetv1 only
         rois = self._region_proposal(net_conv, is_training)
-        if cfg.POOLING_MODE != "crop":
-            raise NotImplementedError
         if fused:
             fc7 = self._fused_tail_entry(net_conv, rois)                # crop commuted past the first 1x1 convs (exact algebra)
         else:
@@ -614,10 +624,17 @@ class Network(object):
     def _check_supported_cfg(mode):
         """Config keys implemented for ONE value only: refuse the others instead of silently ignoring them.  (TRAIN.USE_GT,
         RPN_CLOBBER_POSITIVES, RPN_POSITIVE_WEIGHT, the two INSIDE_WEIGHTS, TRAIN.TRUNCATED and TEST.BBOX_REG are kernel / initialiser
-        arguments since round 3; POOLING_MODE is 'crop' only in the reference as well, network.py:393-396.)"""
+        arguments since round 3; POOLING_MODE is 'crop' only in the reference, network.py:393-396 -- here also 'align', RoIAlign with
+        HIP.ROI_ALIGN_SAMPLES in 1..4 and without RESNET.MAX_POOL; 'pool' and everything else stay refused.)"""
         t = cfg.TRAIN
-        fixed = [("POOLING_MODE", cfg.POOLING_MODE, "crop")]
-        bad = ["%s = %r (only %r is implemented)" % (k, v, want) for k, v, want in fixed if v != want]
+        bad = []
+        if cfg.POOLING_MODE not in ("crop", "align"):
+            bad.append("POOLING_MODE = %r (only 'crop' and 'align' are implemented)" % (cfg.POOLING_MODE,))
+        if cfg.POOLING_MODE == "align":
+            if cfg.HIP.ROI_ALIGN_SAMPLES not in (1, 2, 3, 4):
+                bad.append("HIP.ROI_ALIGN_SAMPLES = %r (1..4 samples per bin side)" % (cfg.HIP.ROI_ALIGN_SAMPLES,))
+            if cfg.RESNET.MAX_POOL:
+                bad.append("RESNET.MAX_POOL = True with POOLING_MODE = 'align' (RoIAlign pools POOLING_SIZE x POOLING_SIZE bins directly)")
         if float(t.RPN_POSITIVE_WEIGHT) >= 0 and not (0.0 < float(t.RPN_POSITIVE_WEIGHT) < 1.0):
             bad.append("TRAIN.RPN_POSITIVE_WEIGHT = %r (the reference asserts 0 < p < 1, anchor_target_layer.py:103-104)" % (t.RPN_POSITIVE_WEIGHT,))
         h = cfg.HIP
@@ -699,7 +716,8 @@ class Network(object):
                 c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH, cfg.TEST.RPN_TOP_N, cfg.POOLING_SIZE,
                 bool(cfg.HIP.WINOGRAD), int(cfg.HIP.WINOGRAD_MIN_CIN), int(cfg.HIP.WINOGRAD_M), tuple(cfg.HIP.WINOGRAD_F2_SCOPES),
                 tuple(cfg.HIP.WINOGRAD_DIRECT_SCOPES), bool(cfg.HIP.WINOGRAD_7X7), bool(cfg.HIP.FUSE_TAIL_MEAN), bool(cfg.HIP.MFMA_X3), bool(cfg.USE_E2E_TF),
-                bool(cfg.HIP.MFMA_H2), bool(cfg.HIP.H2_LAZY_SPLIT), int(cfg.HIP.H2_MIN_TILES), bool(cfg.HIP.H2_TRUNK_PLANES), int(cfg.HIP.H2_TILE_CFG), int(cfg.HIP.X3_TILE_CFG), bool(cfg.HIP.H2_TRAIN))
+                bool(cfg.HIP.MFMA_H2), bool(cfg.HIP.H2_LAZY_SPLIT), int(cfg.HIP.H2_MIN_TILES), bool(cfg.HIP.H2_TRUNK_PLANES), int(cfg.HIP.H2_TILE_CFG), int(cfg.HIP.X3_TILE_CFG), bool(cfg.HIP.H2_TRAIN),
+                cfg.POOLING_MODE, int(cfg.HIP.ROI_ALIGN_SAMPLES))
 
     def shape_scope(self, sess, image_shape, im_info):
         """The buffer scope of one image shape of this network (frcnn_hip/runtime.py Session.shape_scope): at most cfg.HIP.GRAPH_CACHE_SHAPES
@@ -937,7 +955,7 @@ class Network(object):
         t = cfg.TRAIN
         key = ("train_replay", self._tag, tuple(self._image.shape), self._im_info, int(self._gt_boxes.data_ptr()), float(train_op.lr),
                id(train_op), train_op.replay_signature(), hip, self._num_classes, self._anchor_scales, self._anchor_ratios, bool(cfg.RESNET.MAX_POOL),
-               bool(cfg.USE_GPU_NMS), bool(cfg.USE_E2E_TF), cfg.POOLING_SIZE,
+               bool(cfg.USE_GPU_NMS), bool(cfg.USE_E2E_TF), cfg.POOLING_SIZE, cfg.POOLING_MODE,
                (t.RPN_PRE_NMS_TOP_N, t.RPN_POST_NMS_TOP_N, t.RPN_NMS_THRESH, t.BATCH_SIZE, t.FG_FRACTION, t.FG_THRESH, t.BG_THRESH_HI, t.BG_THRESH_LO,
                 t.RPN_BATCHSIZE, t.RPN_FG_FRACTION, t.RPN_POSITIVE_OVERLAP, t.RPN_NEGATIVE_OVERLAP, bool(t.RPN_CLOBBER_POSITIVES),
                 float(t.RPN_POSITIVE_WEIGHT), tuple(t.RPN_BBOX_INSIDE_WEIGHTS), tuple(t.BBOX_INSIDE_WEIGHTS), bool(t.USE_GT),

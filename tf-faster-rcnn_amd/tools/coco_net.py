@@ -17,7 +17,7 @@ import numpy as np
 import _init_paths  # noqa: F401
 import test_net as base
 from frcnn_hip.runtime import Session
-from model.config import cfg, cfg_from_file, cfg_from_list
+from model.config import cfg, cfg_from_file, cfg_from_list, pooling_description
 from model.test import test_net_imdb
 
 
@@ -35,6 +35,7 @@ def main(argv):
         cfg_from_list(args.set_cfgs)
     print("Called with args:\n%s\nUsing config:" % (args,))
     pprint.pprint(cfg)
+    print(pooling_description())
     if not args.imdb_name.startswith("coco_"):
         raise SystemExit("--imdb coco_<year>_<set> (tools/test_net.py takes synthetic_N and voc_<year>_<split>)")
     if args.net not in base.NETS:

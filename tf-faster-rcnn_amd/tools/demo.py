@@ -35,7 +35,7 @@ import sys
 import numpy as np
 
 import _init_paths  # noqa: F401
-from model.config import cfg, cfg_from_file, cfg_from_list
+from model.config import cfg, cfg_from_file, cfg_from_list, pooling_description
 from utils.timer import Timer
 
 CLASSES = ('__background__', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable', 'dog',
@@ -65,6 +65,8 @@ def parse_args(argv):
     ap.add_argument('--flip', action='store_true', help='horizontal-flip ensemble (cfg.HIP.TEST_FLIP): the image and its mirror in one pass')
     ap.add_argument('--vote', type=float, nargs='?', const=0.8, default=None, metavar='THRESH',
                     help='bounding-box voting (cfg.HIP.BBOX_VOTE) with this IoU threshold in (0, 1] (cfg.HIP.BBOX_VOTE_THRESH, 0.8 if omitted)')
+    ap.add_argument('--pooling', choices=('crop', 'align'), default=None,
+                    help="RoI pooling (cfg.POOLING_MODE): 'crop' = tf.image.crop_and_resize, 'align' = RoIAlign; must be what the model was trained with")
     ap.add_argument('--quality', type=int, default=90, help='JPEG quality of the output')
     ap.add_argument('--json', dest='json_path', default=None, help='also write the kept detections of every image to this file')
     ap.add_argument('--cfg', dest='cfg_file', default=None, help='optional config file')
@@ -162,6 +164,10 @@ def main(argv=None, network=None):
     saved = (cfg.TEST.HAS_RPN, cfg.TEST.NMS)
     saved_soft = (cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA)
     saved_tta = (cfg.HIP.TEST_FLIP, cfg.HIP.BBOX_VOTE, cfg.HIP.BBOX_VOTE_THRESH)
+    saved_pooling = cfg.POOLING_MODE
+    if args.pooling is not None:
+        cfg.POOLING_MODE = args.pooling
+    print(pooling_description())
     cfg.TEST.HAS_RPN, cfg.TEST.NMS = True, float(args.nms)                 # demo.py:114; NMS_THRESH
     if args.soft_nms is not None:
         cfg.HIP.SOFT_NMS = SOFT_NMS[args.soft_nms]
@@ -187,6 +193,7 @@ def main(argv=None, network=None):
         cfg.TEST.HAS_RPN, cfg.TEST.NMS = saved
         cfg.HIP.SOFT_NMS, cfg.HIP.SOFT_NMS_SIGMA = saved_soft
         cfg.HIP.TEST_FLIP, cfg.HIP.BBOX_VOTE, cfg.HIP.BBOX_VOTE_THRESH = saved_tta
+        cfg.POOLING_MODE = saved_pooling
     return 0
 
 

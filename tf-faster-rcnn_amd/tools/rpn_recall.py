@@ -29,7 +29,7 @@ import _init_paths  # noqa: F401  (adds tf-faster-rcnn_amd/ and tf-faster-rcnn_a
 from datasets import recall
 from frcnn_hip import ops
 from frcnn_hip.runtime import Session
-from model.config import cfg, cfg_from_file, cfg_from_list
+from model.config import cfg, cfg_from_file, cfg_from_list, pooling_description
 from test_net import NETS
 
 
@@ -177,6 +177,7 @@ def main(argv=None, network=None):
         cfg_from_file(args.cfg_file)
     if args.set_cfgs:
         cfg_from_list(args.set_cfgs)
+    print(pooling_description() + " (the RPN-only pass does not pool; the key only has to be a supported one)")
     from datasets.factory import get_imdb
     imdb = get_imdb(args.imdb_name)
     sess, net = load_network(args, imdb.num_classes) if network is None else network

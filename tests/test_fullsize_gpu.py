@@ -139,7 +139,7 @@ def test_fullsize_batch_invariance_under_the_shipped_configuration(dev, config, 
     launches with at least one 256-row tile per CU, is a function of the launch size) -- must give the same BITS: RPN tensors, proposals,
     head outputs, detections.  The reference is strictly batch-1 (lib/model/test.py:88, lib/nets/network.py:388): a result that
     depends on the neighbours in a launch would make tie-breaks and eps-close NMS decisions depend on them too.  What it takes: the
-    pipe a GEMM runs on and every split-K plan follow the PER-IMAGE shape (lib/nets/network.py _plan_rows, csrc/conv_igemm.hip
+    pipe a GEMM runs on and every split-K plan follow the PER-IMAGE shape (frcnn_hip/forward.py plan_rows, csrc/conv_igemm.hip
     plan_splits), and every tile configuration of a kernel multiplies in the same order (tests/test_h2_gpu.py)."""
     import numpy as np
     import torch

@@ -200,7 +200,7 @@ def test_batched_forward_equals_single_image_forward(small_net):
     """A batch is B independent images whose dense layers share launches; the reference is strictly batch-1 (lib/model/test.py:88).
     The same image must give the same BITS alone and in any slot of a batch -- under the shipped configuration (h2 + x3 + Winograd),
     with h2 forced onto every eligible layer (H2_MIN_TILES = 1), with x3 only, and with every product on the f32 MFMA: the pipe a GEMM
-    runs on and the split-K plan of a convolution follow the per-image shape (network.py _plan_rows, conv_igemm.hip plan_splits), and
+    runs on and the split-K plan of a convolution follow the per-image shape (frcnn_hip/forward.py plan_rows, conv_igemm.hip plan_splits), and
     the tile configurations of one kernel all multiply in the same order."""
     sess, net, image, im_info = small_net
     rng = np.random.RandomState(9)
@@ -454,7 +454,7 @@ def test_fused_tail_mean_matches_the_unfused_path(small_net):
 def test_h2_static_filter_criterion_falls_back_to_x3(dev):
     """A consumer filter whose entries for one input channel are below 2^-18 of the rest (the signature of an activation channel
     2^18 times the others) keeps that layer, and the producer feeding it, off the block-scaled fp16x2 format: the exact x3 split runs
-    instead (Session.h2_channel_spread, Network._h2_eligible); 2^-17 still runs in frcnn_gemm_h2.  Both give the f32-class result."""
+    instead (Session.h2_channel_spread, frcnn_hip/forward.py h2_rule); 2^-17 still runs in frcnn_gemm_h2.  Both give the f32-class result."""
     from frcnn_hip.runtime import Session
     from model.config import cfg
     from nets.resnet_v1 import resnetv1

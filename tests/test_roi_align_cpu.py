@@ -261,12 +261,14 @@ class _Sess(object):
 
 @pytest.mark.parametrize("mode", ["align", "crop"])
 def test_train_tape_holds_one_pooling_record_of_the_mode(restore_cfg, mode):
+    from frcnn_hip import forward
     cfg = restore_cfg
     cfg.POOLING_MODE = mode
     for make in _nets():
         net = make()
         net.create_architecture("TRAIN", 21, tag="t")
-        net._sess, net._tape, net._requires_grad, net._h2_of, net._f32_missing = _Sess(), [], set(), {}, set()
+        net._sess, net._tape, net._requires_grad = _Sess(), [], set()
+        net._forms = forward.Forms(None, net._sess, "t", False)
         net._feat_stride = [16]
         bottom, rois = torch.zeros(1, H, W, 8), torch.zeros(6, 5)
         net._requires_grad.add(bottom.data_ptr())

@@ -73,14 +73,15 @@ def test_six_term_product_drops_at_most_one_f32_rounding():
 
 
 def test_host_rule_for_x3_launches():
+    from frcnn_hip import forward
     from model.config import cfg
-    from nets.resnet_v1 import resnetv1
-    net = resnetv1(101)
-    net._mode = "TEST"
+    mode = ["TEST"]
     old = cfg.HIP.MFMA_X3
     try:
         cfg.HIP.MFMA_X3 = True
-        ok = net._x3_eligible
+
+        def ok(M, N, K, G):             # (frcnn_hip/forward.py x3_rule under the plan of the switches as they are, no batch context)
+            return forward.x3_rule(forward.make_plan(mode[0], 0, cfg.HIP), M, N, K, G)
         assert ok(4 * 2394, 256, 1024, 1)              # block3 conv1, 4 images: 75 x 2 = 150 tiles
         assert not ok(2394, 256, 1024, 1)              # one image: 38 tiles -> the split-K f32 launch
         assert ok(2394, 1024, 256, 1)                  # block3 conv3, one image: 152 tiles
@@ -88,9 +89,9 @@ def test_host_rule_for_x3_launches():
         assert ok(150000, 64, 256, 1)                  # Cout = 64: 128 x 64 tiles
         assert not ok(9576, 18, 512, 1) and not ok(9576, 36, 512, 1)            # RPN heads: Cout not a multiple of 64
         assert not ok(9576, 256, 1000, 1)              # K % 32
-        net._mode = "TRAIN"
+        mode[0] = "TRAIN"
         assert not ok(4 * 14700, 512, 2048, 1)         # filters change every step
-        net._mode = "TEST"
+        mode[0] = "TEST"
         cfg.HIP.MFMA_X3 = False
         assert not ok(4 * 14700, 512, 2048, 1)
     finally:

@@ -467,7 +467,7 @@ class Session(VariableStore):
         arithmetic on the variables, once per scope.  A trained network with outlier activation channels (1e3 ... 1e5 times the rest)
         carries correspondingly small filter entries for them in the consumer; below 2^-18 the block-scaled fp16x2 format of
         frcnn_gemm_h2 would hold those entries (and the non-outlier activations sharing a 128-k block with the outlier) to fewer bits
-        than float32 does, so such a layer stays on the exact x3 split (lib/nets/network.py _h2_eligible)."""
+        than float32 does, so such a layer stays on the exact x3 split (frcnn_hip/forward.py h2_rule)."""
         got = self.h2_spread.get(scope)
         if got is None:
             w = np.abs(self.variables[scope + "/weights"].astype(np.float64))

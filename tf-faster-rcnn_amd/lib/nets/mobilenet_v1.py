@@ -69,25 +69,20 @@ class mobilenetv1(Network):
         pad = (1, 1, 1, 1)                                   # SAME (stride 1) == explicit pad 1 (stride 2) for k=3
         OH, OW = ops.conv_out_size(H, 3, stride, 1, 1), ops.conv_out_size(W, 3, stride, 1, 1)
         out = self._sess.buf(self._tag + "/" + dw_scope, (N, OH, OW, C))
-        self._need_f32(x)
-        cout = self._depth(_SEP[i - 1][1])
-        if C % 128 == 0 and self._h2_eligible(N * OH * OW, cout, C, 1, "%s/Conv2d_%d_pointwise" % (s, i)):
+        self._forms.need_f32(x)
+        if self._pointwise_route("%s/Conv2d_%d_pointwise" % (s, i), N * OH * OW, C, self._depth(_SEP[i - 1][1])) == "h2":
             # cfg.HIP.MFMA_H2: the depthwise kernel hands the pointwise convolution its operand planes; in TEST mode that is the only
             # reader, so no float32 tensor is written (TRAIN: the tape needs it -- both forms)
             yp = self._sess.h2_buf(self._tag + "/" + dw_scope, N * OH * OW, C)
             keep = self._mode == "TRAIN"
             self._sess.mark("op:dwconv3x3", 0, lambda: ops.dwconv3x3(x, w, b, stride, pad, ACT_RELU6, out=out, out_planes=yp, want_f32=keep),
                             nbytes=4 * (x.numel() + out.numel() * (2 if keep else 1)))
-            self._wrote(out, yp, keep)
-            y = out
+            self._forms.wrote(out, yp, keep)
         else:
-            y = self._sess.mark("op:dwconv3x3", 0, lambda: ops.dwconv3x3(x, w, b, stride, pad, ACT_RELU6, out=out), nbytes=4 * (x.numel() + out.numel()))
-            self._wrote(out)
-        if self._mode == "TRAIN":
-            self._tape.append(dict(kind="dwconv", scope=dw_scope, x=x, y=out, stride=stride, pad=pad, act=ACT_RELU6))
-            if self.trainable_scope(dw_scope) or x.data_ptr() in self._requires_grad:
-                self._requires_grad.add(out.data_ptr())
-        return self._conv(y, "%s/Conv2d_%d_pointwise" % (s, i), 1, act=ACT_RELU6, bn_eps=BN_EPS)
+            self._sess.mark("op:dwconv3x3", 0, lambda: ops.dwconv3x3(x, w, b, stride, pad, ACT_RELU6, out=out), nbytes=4 * (x.numel() + out.numel()))
+            self._forms.wrote(out)
+        self._record("dwconv", out, (x,), scope=dw_scope, x=x, stride=stride, pad=pad, act=ACT_RELU6)
+        return self._conv(out, "%s/Conv2d_%d_pointwise" % (s, i), 1, act=ACT_RELU6, bn_eps=BN_EPS)
 
     _trainable_on_device = True
 
@@ -125,10 +120,4 @@ class mobilenetv1(Network):
         net = pool5
         for i in (12, 13):
             net = self._separable(net, i, _SEP[i - 1][0])
-        out = self._sess.buf(self._tag + "/fc7", (net.shape[0], net.shape[-1]))
-        res = self._sess.mark("op:spatial_mean", 0, lambda: ops.spatial_mean(net, out=out), nbytes=4 * (net.numel() + out.numel()))
-        if self._mode == "TRAIN":
-            self._tape.append(dict(kind="mean", x=net, y=res, name=self._scope + "/fc7_mean"))
-            if net.data_ptr() in self._requires_grad:
-                self._requires_grad.add(res.data_ptr())
-        return res
+        return self._spatial_mean(net)

@@ -15,7 +15,7 @@ import collections
 import numpy as np
 import torch
 
-from frcnn_hip import ACT_NONE, ACT_RELU, NMS_RULE_CPU, NMS_RULE_GPU, ops
+from frcnn_hip import ACT_NONE, ACT_RELU, NMS_RULE_CPU, NMS_RULE_GPU, forward, ops
 from frcnn_hip.runtime import VarSpec
 from model.config import cfg
 
@@ -42,10 +42,8 @@ class Network(object):
         self.replay_stats = dict(eager=0, recorded=0, replayed=0)      # train_step_async under cfg.HIP.TRAIN_REPLAY
         self._replay_clock, self._train_arena, self._train_scope_key = 0, None, None     # LRU clock of the recordings, replay.Arena, the step's shape scope
         self._train_state = None               # the solver handle of the last train_step_with_summary (get_summary's regulariser term)
-        self._plan_batch = 0                   # images per launch that TEST-mode launch-size rules see (_plan_context); 0: as built
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
-        self._h2_of = {}                       # activation address -> ops.H2 operand planes of that tensor (cfg.HIP.MFMA_H2)
-        self._f32_missing = set()              # addresses of activations that exist ONLY as operand planes (never read as f32)
+        self._plan, self._forms = None, None   # the last graph build's forward.Plan and forward.Forms (_plan_context)
 
     # ------------------------------------------------------------------ variable declaration
     def _var(self, name, shape, init, arg=None):
@@ -77,230 +75,43 @@ class Network(object):
     # ------------------------------------------------------------------ building blocks
     def _conv(self, x, scope, k, stride=1, pad=(0, 0, 0, 0), act=ACT_RELU, bn_eps=None, residual=None,
               res_stride=1, fold_w=False, out_affine=None, real_cin=None, no_bias=False, emit_h2=False, want_f32=True):
-        """emit_h2 / want_f32 (cfg.HIP.MFMA_H2, TEST mode): the caller knows the consumers of the result -- emit_h2: a frcnn_gemm_h2
-        launch will read it, so the producer writes its operand planes from its epilogue; want_f32 = False: nothing reads the
-        float32 tensor (honoured only where the planes are emitted)."""
-        sess = self._sess
+        """One convolution on the route forward.conv_route names; emit_h2 / want_f32: what the caller knows about the consumers of the
+        result (frcnn_hip/forward.py, "the routes")."""
         N, H, W, Cin = x.shape
-        wino = (cfg.HIP.WINOGRAD and k == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1)
-                and residual is None and not fold_w and out_affine is None and not no_bias
-                and Cin % 32 == 0 and Cin >= cfg.HIP.WINOGRAD_MIN_CIN and act in (ACT_NONE, ACT_RELU)
-                and not any(tok in scope for tok in cfg.HIP.WINOGRAD_DIRECT_SCOPES))
-        if wino and self._mode == "TEST":
-            return self._conv_winograd(x, scope, act, bn_eps, emit_h2, want_f32)
-        wino = wino and cfg.HIP.WINOGRAD_TRAIN
-        w, b = sess.conv_params(scope, bn_eps=bn_eps, fold_w=fold_w,
-                                out_scale=None if out_affine is None else out_affine[0],
-                                out_shift=None if out_affine is None else out_affine[1])
-        if no_bias:
-            b = None
-        N, H, W, Cin = x.shape
-        OH = ops.conv_out_size(H, k, stride, pad[0], pad[1])
-        OW = ops.conv_out_size(W, k, stride, pad[2], pad[3])
-        Cout = w.shape[0]
-        out = sess.buf(self._tag + "/" + scope, (N, OH, OW, Cout))
-        flops = 2 * N * OH * OW * Cout * k * k * (Cin if real_cin is None else real_cin)
-        plain = k == 1 and stride == 1 and tuple(pad) == (0, 0, 0, 0) and not fold_w and (residual is None or res_stride == 1)
-        M = N * OH * OW
-        if wino:
-            # TRAIN: the filter changes every step -> transform the live (folded) device filter, then the same Winograd chain
-            m = self._winograd_scheme(scope, H, W)
-            G, T = ops.winograd_points(m), ops.winograd_tiles(N, H, W, m)
-            # (weight-only: after the first step the solver has it re-run beside the forward pass, frcnn_hip/runtime.py PreparedFilters)
-            u = sess.prepared.get(("fwd", "wino_u", self._tag, scope, m), lambda: ops.winograd_filter_transform_device(
-                w, m, False, out=sess.buf(self._tag + "/wino_u/" + scope, (G, Cout, Cin))))
-            mm = sess.buf(self._tag + "/wino_m", (G, T, Cout))
-            v = sess.buf(self._tag + "/wino_v", (G, T, Cin))
-            # emit_h2: the output transform writes the float32 tensor (the tape needs it) AND the operand planes of the 1x1 that follows
-            yp = sess.h2_buf(self._tag + "/" + scope, M, Cout) if (emit_h2 and cfg.HIP.MFMA_H2 and Cout % 128 == 0) else None
-            sess.mark("conv:" + scope, 2 * G * T * Cout * Cin,
-                      lambda: ops.conv3x3_winograd(x, u, b, act, out=out, v_buf=v, m_buf=mm, out_planes=yp),
-                      nbytes=4 * (v.numel() + u.numel() + mm.numel()))
-            self._wrote(out, yp, True) if yp is not None else self._wrote(out)
-        elif plain and self._h2_eligible(M, Cout, Cin, 1, scope) and self._h2_input(x) is not None:
-            # a plain GEMM with a static filter on the fp16 matrix pipe, block-scaled two-piece operands (cfg.HIP.MFMA_H2)
-            xp, wp = self._h2_input(x), sess.h2_planes(w)
-            yp = sess.h2_buf(self._tag + "/" + scope, M, Cout) if emit_h2 else None
-            y = out if (want_f32 or yp is None or self._mode == "TRAIN") else None
-            res = residual
-            if residual is not None and residual.data_ptr() in self._f32_missing:
-                res = self._h2_of[residual.data_ptr()]              # the trunk exists as operand planes only (cfg.HIP.H2_TRUNK_PLANES)
-            tcfg = int(cfg.HIP.H2_TILE_CFG)
-            sess.mark("conv:h2:" + scope, flops, lambda: ops.gemm_h2(xp, wp, 1, M, Cout, Cin, b, res, act, out=y, out_planes=yp,
-                                                                      want_f32=False, cfg=tcfg),
-                      nbytes=4 * M * Cin + 4 * w.numel() + (4 * out.numel() if y is not None else 0)
-                      + (4 * out.numel() if yp is not None else 0) + (4 * out.numel() if residual is not None else 0))
-            self._wrote(out, yp, y is not None)
-        elif plain and self._x3_eligible(M, Cout, Cin, 1):
-            # ... on the bf16 matrix pipe with exact bf16x3 operand splits (cfg.HIP.MFMA_X3)
-            self._need_f32(x), self._need_f32(residual)
-            planes = sess.x3_planes(w)
-            xc = int(cfg.HIP.X3_TILE_CFG)
-            sess.mark("conv:x3:" + scope, flops, lambda: ops.gemm_x3(x, planes, 1, M, Cout, Cin, b, residual, act, out=out, cfg=xc),
-                      nbytes=4 * (x.numel() + out.numel() + (out.numel() if residual is not None else 0)) + 6 * w.numel())
-            self._wrote(out)
-        else:
-            self._need_f32(x), self._need_f32(residual)
-            sess.mark("conv:" + scope, flops,
-                      lambda: ops.conv2d(x, w, b, k, k, stride, pad, act, residual, res_stride, fold_w, out=out),
-                      nbytes=4 * (x.numel() + w.numel() + out.numel() + (out.numel() if residual is not None else 0)))
-            self._wrote(out)
+        M = N * ops.conv_out_size(H, k, stride, pad[0], pad[1]) * ops.conv_out_size(W, k, stride, pad[2], pad[3])
+        route = forward.conv_route(self._plan, scope, k, stride, pad, act, Cin, self._var_specs[scope + "/weights"].shape[-1], M, residual is not None,
+                                   res_stride, fold_w, out_affine is not None, no_bias, self._spread(scope), self._forms.has_planes(x) or self._plan.h2_lazy_split)
+        out = forward.CONV[route](ops, self._sess, self._plan, self._forms, self._tag, scope, x, k, stride, pad, act, bn_eps, residual,
+                                  res_stride, fold_w, out_affine, real_cin, no_bias, emit_h2, want_f32)
+        return self._record("conv", out, (x, residual), scope=scope, x=x, k=k, stride=stride, pad=tuple(pad), act=act, residual=residual,
+                            res_stride=res_stride)
+
+    def _record(self, kind, y, sources, **fields):
+        """TRAIN mode: the tape record of the launches that wrote y; y takes a gradient when one of its sources does, or when the record
+        names a filter (`scope`) the solver updates."""
         if self._mode == "TRAIN":
-            self._tape.append(dict(kind="conv", scope=scope, x=x, y=out, k=k, stride=stride, pad=tuple(pad), act=act,
-                                   residual=residual, res_stride=res_stride))
-            if self.trainable_scope(scope) or x.data_ptr() in self._requires_grad:
-                self._requires_grad.add(out.data_ptr())
-            if residual is not None and residual.data_ptr() in self._requires_grad:
-                self._requires_grad.add(out.data_ptr())
-        return out
+            self._tape.append(dict(fields, kind=kind, y=y))
+            if ("scope" in fields and self.trainable_scope(fields["scope"])) or any(s is not None and s.data_ptr() in self._requires_grad for s in sources):
+                self._requires_grad.add(y.data_ptr())
+        return y
 
-    # ---- cfg.HIP.MFMA_H2 plumbing -------------------------------------------------------------------------------------------------
-    H2_MIN_CHANNEL_RATIO = 2.0 ** -18      # see Session.h2_channel_spread
+    def _spread(self, scope):
+        return forward.channel_spread(self._sess, self._plan, scope)
 
-    def _h2_eligible(self, M, N, K, G, scope=None):
-        """K % 128 == 0 (scale blocks), N % 128 == 0 (tiles), enough tiles to fill the chip, and the 32-bit offset limits of
-        frcnn_gemm_h2.  TEST mode: static filters, split once.  TRAIN mode (cfg.HIP.H2_TRAIN): the pointwise convolutions of the
-        forward pass take the same kernel -- the solver re-splits the updated filters after every step (Session.h2_refresh), the
-        float32 outputs the tape needs are always written, inputs without planes are split by a separate pass."""
-        rows = G * M
-        if scope is not None and self._mode == "TEST" and self._sess.h2_channel_spread(scope) < self.H2_MIN_CHANNEL_RATIO:
-            return False              # a filter whose entries for one input channel are < 2^-18 of the rest: exact x3 split instead
-        return (bool(cfg.HIP.MFMA_H2) and (self._mode == "TEST" or bool(cfg.HIP.H2_TRAIN)) and K % 128 == 0 and N % 128 == 0
-                and ((self._plan_rows(M) + 127) // 128) * (N // 128) * G >= self._h2_min_tiles()
-                and 4 * rows * K < (1 << 32) and 4 * N * K < (1 << 32) and M * N < (1 << 29))
+    def _pointwise_route(self, scope, M, Cin, Cout, res_stride=None):
+        """The route of the 1x1 / stride 1 convolution `scope` of [M,Cin] -> [M,Cout] (res_stride: of its residual, None = it has none) when
+        its input exists as operand planes: what a producer asks about its consumer, answered by the consumer's own rule."""
+        return forward.conv_route(self._plan, scope, 1, 1, forward.ZERO_PAD, ACT_RELU, Cin, Cout, M, res_stride is not None, res_stride,
+                                  spread=self._spread(scope))
 
-    @staticmethod
-    def h2_min_tiles(mode):
-        """Tiles a launch must have to take frcnn_gemm_h2.  TEST: cfg.HIP.H2_MIN_TILES.  TRAIN (one image per step): cfg.HIP.H2_TRAIN_MIN_TILES,
-        or -- when that is None -- the same knob as TEST mode (tests force the kernel onto toy TRAIN networks with H2_MIN_TILES = 1 and
-        H2_TRAIN_MIN_TILES = None).  Each value means what it says: no comparison against a default."""
-        if mode == "TRAIN" and cfg.HIP.H2_TRAIN_MIN_TILES is not None:
-            return int(cfg.HIP.H2_TRAIN_MIN_TILES)
-        return int(cfg.HIP.H2_MIN_TILES)
+    def _mean_fusable(self, rows, cout, cin, scope, group_rows):
+        return forward.mean_fusable(self._plan, rows, cout, cin, group_rows, self._spread(scope))
 
-    def _h2_min_tiles(self):
-        return self.h2_min_tiles(self._mode)
-
-    def _h2_input(self, x):
-        """Operand planes of activation x: those its producer emitted, else (cfg.HIP.H2_LAZY_SPLIT) a frcnn_h2_split pass, else None."""
-        xp = self._h2_of.get(x.data_ptr())
-        if xp is None and cfg.HIP.H2_LAZY_SPLIT:
-            self._need_f32(x)
-            K = x.shape[-1]
-            xp = self._sess.h2_buf(self._tag + "/split@%x" % x.data_ptr(), x.numel() // K, K)
-            self._sess.mark("op:h2_split", 0, lambda: ops.h2_split(x, out=xp), nbytes=8 * x.numel())
-            self._h2_of[x.data_ptr()] = xp
-        return xp
-
-    def _wrote(self, t, planes=None, f32=True):
-        """Every launch that writes activation t reports it: planes derived from an earlier write are dropped (buffers are static
-        and sub-graphs may be re-run on new inputs), planes this launch emitted are registered."""
-        k = t.data_ptr()
-        if planes is None:
-            self._h2_of.pop(k, None)
-        else:
-            self._h2_of[k] = planes
-        (self._f32_missing.discard if f32 else self._f32_missing.add)(k)
-        return t
-
-    def _need_f32(self, x):
-        if x is not None and x.data_ptr() in self._f32_missing:
-            raise RuntimeError("graph construction error: a float32 consumer reads a tensor that was emitted as operand planes only")
-
-    def _x3_eligible(self, M, N, K, G):
-        """cfg.HIP.MFMA_X3: TEST mode (static filters), N % 64 == 0, K % 32 == 0 and at least 150 tiles of 128 x 128 -- below that
-        the split-K f32 launches are as fast (profiles/r02_m_x3_sweep.txt, single-image rows)."""
-        return (bool(cfg.HIP.MFMA_X3) and self._mode == "TEST" and N % 64 == 0 and K % 32 == 0
-                and ((self._plan_rows(M) + 127) // 128) * ((N + 127) // 128) * G >= 150 and M * N < (1 << 31) and N * K < (1 << 28))
-
-    @staticmethod
-    def _winograd_scheme(scope, H, W):
-        """2 / 4 = F(m x m,3x3) tiles; 7 = the mixed F(4,3)+F(3,3) scheme for 7x7 maps (121 instead of 144 GEMM rows per RoI)."""
-        if any(tok in scope for tok in cfg.HIP.WINOGRAD_F2_SCOPES):
-            return 2
-        m = int(cfg.HIP.WINOGRAD_M)
-        return 7 if (m == 4 and H == 7 and W == 7 and cfg.HIP.WINOGRAD_7X7) else m
-
-    def _conv_winograd(self, x, scope, act, bn_eps, emit_h2=False, want_f32=True):
-        """3x3 / stride 1 / SAME convolution as Winograd F(m x m,3x3): input transform -> (m+2)^2 GEMMs in ONE launch of
-        the f32-MFMA kernel -> output transform with bias + ReLU.  Exact algebra in f32; m = 2 (2.25x fewer
-        multiplications, rounding like the direct kernel) or m = 4 (4x fewer; a single layer rounds ~10x worse than
-        direct, but through the full ResNet-101 the outputs move by ~1e-6 relative, profiles/r01_e_winograd_error.txt).
-        cfg.HIP.MFMA_H2: the input transform emits V as operand planes, the products run in frcnn_gemm_h2, and (emit_h2) the
-        output transform emits the result as the next 1x1 convolution's operand planes."""
-        sess = self._sess
-        self._need_f32(x)
-        N, H, W, Cin = x.shape
-        m = self._winograd_scheme(scope, H, W)
-        u, b = sess.winograd_params(scope, bn_eps=bn_eps, m=m)
-        G, Cout = u.shape[0], u.shape[1]
-        T = ops.winograd_tiles(N, H, W, m)
-        out = sess.buf(self._tag + "/" + scope, (N, H, W, Cout))
-        flops = 2 * G * T * Cout * Cin
-        if (cfg.HIP.WINOGRAD_FUSED_F2 and m == 2 and Cin == 64 and Cout == 64 and self._mode == "TEST" and self._x3_eligible(T, Cout, Cin, G)
-                and N * H * W < (1 << 23)):
-            # block1's conv2: transforms and products in one launch, the bits of the three launches below (csrc/winograd2_fused.hip)
-            planes = sess.x3_planes(u)
-            sess.mark("conv:x3:" + scope, flops, lambda: ops.winograd2_conv_x3(x, planes, b, act, out),
-                      nbytes=4 * (x.numel() + out.numel()) + 6 * u.numel())
-            return self._wrote(out)
-        mm = sess.buf(self._tag + "/wino_m", (G, T, Cout))
-        if self._h2_eligible(T, Cout, Cin, G, scope):
-            vp, wp = sess.h2_buf(self._tag + "/wino_v", G * T, Cin), sess.h2_planes(u)
-            sess.mark("op:wino_in", 0, lambda: ops.winograd_input_transform_h2(x, vp, m), nbytes=4 * (x.numel() + G * T * Cin))
-            tcfg = int(cfg.HIP.H2_TILE_CFG)
-            sess.mark("conv:h2:" + scope, flops, lambda: ops.gemm_h2(vp, wp, G, T, Cout, Cin, out=mm, cfg=tcfg),
-                      nbytes=4 * (G * T * Cin + mm.numel()) + 4 * u.numel())
-        else:
-            v = sess.buf(self._tag + "/wino_v", (G, T, Cin))
-            sess.mark("op:wino_in", 0, lambda: ops.winograd_input_transform(x, v, m), nbytes=4 * (x.numel() + v.numel()))
-            if self._x3_eligible(T, Cout, Cin, G):
-                planes = sess.x3_planes(u)
-                xc = int(cfg.HIP.X3_TILE_CFG)
-                sess.mark("conv:x3:" + scope, flops, lambda: ops.gemm_x3(v, planes, G, T, Cout, Cin, out=mm, cfg=xc),
-                          nbytes=4 * (v.numel() + mm.numel()) + 6 * u.numel())
-            else:
-                sess.mark("conv:" + scope, flops, lambda: ops.gemm_batched_nt(v, u, mm), nbytes=4 * (v.numel() + u.numel() + mm.numel()))
-        if emit_h2 and cfg.HIP.MFMA_H2 and Cout % 128 == 0:
-            yp = sess.h2_buf(self._tag + "/" + scope, N * H * W, Cout)
-            y = out if want_f32 else None
-            sess.mark("op:wino_out", 0, lambda: ops.winograd_output_transform_h2(mm, b, act, (N, H, W, Cout), m, yp, y),
-                      nbytes=4 * (mm.numel() + out.numel() * (2 if want_f32 else 1)))
-            self._wrote(out, yp, y is not None)
-        else:
-            sess.mark("op:wino_out", 0, lambda: ops.winograd_output_transform(mm, b, act, out, m), nbytes=4 * (mm.numel() + out.numel()))
-            self._wrote(out)
-        return out
-
-    def _conv1x1_mean(self, x, scope, group_rows, act=ACT_RELU, bn_eps=None, residual=None, name="fc7"):
-        """The tail's last 1x1 convolution fused with reduce_mean over the P*P positions of every RoI (resnet_v1.py:115-125), TEST mode,
-        cfg.HIP.FUSE_TAIL_MEAN: frcnn_gemm_h2_mean -- the [R*P*P, Cout] tensor is never written or re-read.  One batch entry per IMAGE:
-        a RoI's rows are added in an order that depends on its index inside its image only, so batch slots and batch sizes do not
-        change a bit of fc7 (the caller checks _mean_fusable first: the layer must be h2-eligible and x must exist as operand planes)."""
-        sess = self._sess
-        w, b = sess.conv_params(scope, bn_eps=bn_eps)
-        Cin, Cout = x.shape[-1], w.shape[0]
-        rows = x.numel() // Cin
-        G = max(1, self._plan_batch)
-        assert rows % G == 0 and (rows // G) % group_rows == 0
-        M = rows // G
-        out = sess.buf(self._tag + "/" + name, (rows // group_rows, Cout))
-        xp, wp = self._h2_of[x.data_ptr()], sess.h2_planes(w)
-        res = residual
-        if residual is not None and residual.data_ptr() in self._f32_missing:
-            res = self._h2_of[residual.data_ptr()]
-        tcfg = int(cfg.HIP.H2_TILE_CFG)
-        sess.mark("conv:h2:" + scope, 2 * rows * Cout * Cin, lambda: ops.gemm_h2_mean(xp, wp, G, M, Cout, Cin, b, res, act, group_rows, out=out, cfg=tcfg),
-                  nbytes=4 * (rows * Cin + w.numel() + out.numel() + (rows * Cout if residual is not None else 0)))
-        return self._wrote(out)
-
-    def _mean_fusable(self, rows, cout, cin, scope, group_rows=1):
-        """cfg.HIP.FUSE_TAIL_MEAN applies where the tail's last convolution runs in frcnn_gemm_h2 (TEST mode, h2-eligible shape and filter)
-        and the RoI rows split evenly over the images of the batch (whole groups of `group_rows` rows per image)."""
-        G = max(1, self._plan_batch)
-        return (bool(cfg.HIP.FUSE_TAIL_MEAN) and self._mode == "TEST" and rows % G == 0 and (rows // G) % max(1, int(group_rows)) == 0
-                and self._h2_eligible(rows, cout, cin, 1, scope)
-                and bool(cfg.HIP.H2_LAZY_SPLIT or cfg.HIP.WINOGRAD))         # its input must exist as planes: emitted by the Winograd conv2, or split lazily
+    def _spatial_mean(self, x):
+        """reduce_mean over the positions of every RoI (resnet_v1.py:124) -> fc7 [R, C]"""
+        out = self._sess.buf(self._tag + "/fc7", (x.shape[0], x.shape[-1]))
+        self._sess.mark("op:spatial_mean", 0, lambda: ops.spatial_mean(x, out=out), nbytes=4 * (x.numel() + out.numel()))
+        return self._record("mean", out, (x,), x=x, name=self._scope + "/fc7_mean")
 
     # ------------------------------------------------------------------ ImageNet-pretrained weights (train_val.py:177-202)
     _rgb_first_conv = None                   # scope tail of the stem conv whose input channels are RGB in the released weights
@@ -464,7 +275,7 @@ class Network(object):
     def _crop_images(self, bottom, rois, out, max_pool=False, bias=None, act=ACT_NONE):
         """tf.image.crop_and_resize(bottom, boxes, box_ind = rois[:,0]) (network.py:141-157) for the whole batch in one launch."""
         fs, P = float(self._feat_stride[0]), cfg.POOLING_SIZE
-        self._need_f32(bottom)
+        self._forms.need_f32(bottom)
         nbytes = 4 * (bottom.numel() + out.numel())
         if cfg.POOLING_MODE == "align":              # csrc/roialign_math.h; max_pool does not apply (see _crop_pool)
             S = int(cfg.HIP.ROI_ALIGN_SAMPLES)
@@ -473,7 +284,7 @@ class Network(object):
             self._sess.mark("op:crop_and_resize", 0, lambda: ops.crop_and_resize(bottom, rois, fs, P, max_pool=max_pool, out=out), nbytes=nbytes)
         else:
             self._sess.mark("op:crop_and_resize", 0, lambda: ops.crop_and_resize_bias_act(bottom, rois, fs, P, bias, act, out=out), nbytes=nbytes)
-        return self._wrote(out)
+        return self._forms.wrote(out)
 
     def _crop_pool_layer(self, bottom, rois, name):
         # network.py:141-157: 14x14 crop + 2x2 max pool (TEST: fused in one kernel)
@@ -489,21 +300,14 @@ class Network(object):
             # RoIAlign in its standard form for every backbone: POOLING_SIZE x POOLING_SIZE bins of S x S samples, no 14x14 + 2x2 max detour
             S = int(cfg.HIP.ROI_ALIGN_SAMPLES)
             out = self._crop_images(bottom, rois, self._sess.buf(self._tag + "/" + name, (R, P, P, C)))
-            if self._mode == "TRAIN":
-                self._tape.append(dict(kind="roi_align", feat=bottom, rois=rois, y=out, stride=fs, samples=S))
-                if bottom.data_ptr() in self._requires_grad:
-                    self._requires_grad.add(out.data_ptr())
-            return out
+            return self._record("roi_align", out, (bottom,), feat=bottom, rois=rois, stride=fs, samples=S)
         if self._mode != "TRAIN":
             return self._crop_images(bottom, rois, self._sess.buf(self._tag + "/" + name, (R, P, P, C)), max_pool=max_pool)
         pre = 2 * P if max_pool else P
         crop = self._sess.buf(self._tag + "/" + name + ("/crop" if max_pool else ""), (R, pre, pre, C))
         self._sess.mark("op:crop_and_resize", 0, lambda: ops.crop_and_resize(bottom, rois, fs, pre, max_pool=False, out=crop),
                         nbytes=4 * (bottom.numel() + crop.numel()))
-        self._wrote(crop)
-        self._tape.append(dict(kind="crop", feat=bottom, rois=rois, y=crop, stride=fs))
-        if bottom.data_ptr() in self._requires_grad:
-            self._requires_grad.add(crop.data_ptr())
+        self._record("crop", self._forms.wrote(crop), (bottom,), feat=bottom, rois=rois, stride=fs)
         return self._max_pool(crop, 2, 2, name) if max_pool else crop
 
     def _max_pool(self, x, k, stride, name):
@@ -513,12 +317,7 @@ class Network(object):
         out = self._sess.buf(self._tag + "/" + name, (N, OH, OW, C))
         pad = (0, (OH - 1) * stride + k - H, 0, (OW - 1) * stride + k - W)
         self._sess.mark("op:maxpool", 0, lambda: ops.maxpool(x, k, stride, pad, out=out), nbytes=4 * (x.numel() + out.numel()))
-        self._wrote(out)
-        if self._mode == "TRAIN":
-            self._tape.append(dict(kind="maxpool", x=x, y=out, k=k, stride=stride, name=name))
-            if x.data_ptr() in self._requires_grad:
-                self._requires_grad.add(out.data_ptr())
-        return out
+        return self._record("maxpool", self._forms.wrote(out), (x,), x=x, k=k, stride=stride, name=name)
 
     def weight_decay_for(self, scope):
         """L2 coefficient of one layer's weights; None = cfg.TRAIN.WEIGHT_DECAY (network.py:303-311 arg_scope)."""
@@ -568,26 +367,19 @@ class Network(object):
     def _head_to_tail(self, pool5, is_training, reuse=None):
         raise NotImplementedError
 
-    PLAN_IMAGES = 4        # csrc/conv_igemm.hip PLAN_IMAGES: every launch-size rule is evaluated for a batch of this many images
-
-    def _plan_rows(self, M):
-        """Rows of a launch as they would be in a PLAN_IMAGES-image batch.  Which matrix pipe a GEMM runs on (>= 150 tiles: h2 / x3) and
-        whether a convolution is cut along K change the bits of the result, so neither may depend on how many images share the launch:
-        TEST-mode rules see per-image rows x PLAN_IMAGES whatever the batch is (the reference is strictly batch-1, lib/model/test.py:88;
-        the same image must give the same tensors at batch 1, in any slot of a batch of 4, or of 8)."""
-        B = self._plan_batch
-        return M // B * self.PLAN_IMAGES if (B > 0 and M % B == 0) else M
-
     class _plan_context(object):
-        """The batch-invariant launch plan around a graph build: TEST-mode rules (matrix pipe, split-K plan, f32 tile configuration)
-        see the PER-IMAGE shape whatever the batch is -- _plan_rows here, launch context key 8 inside the library."""
+        """The batch-invariant launch plan around a graph build: TEST-mode rules (matrix pipe, split-K plan, f32 tile configuration) see the
+        PER-IMAGE shape whatever the batch is -- forward.plan_rows here, launch context key 8 inside the library.  Entering it starts a build: the
+        network gets the build's Plan (the switches as they are now) and an empty Forms, and keeps both (a sub-graph re-run later continues them)."""
 
         def __init__(self, net, is_training):
             self.net, self.batch = net, 0 if is_training else int(net._image.shape[0])
 
         def __enter__(self):
             from frcnn_hip import lib
-            self.net._plan_batch = self.batch
+            net = self.net
+            net._plan = forward.make_plan(net._mode, self.batch, cfg.HIP)
+            net._forms = forward.Forms(ops, net._sess, net._tag, net._plan.h2_lazy_split)
             lib().frcnn_set_tuning(8, self.batch)        # the same rule inside the library (split-K plan of frcnn_conv2d_nhwc_ws)
 
         def __exit__(self, *exc):
@@ -603,7 +395,6 @@ class Network(object):
         self._tape = []
         self._requires_grad = set()
         self._act_summaries = []                        # this build's [head, rpn] (the backbones and _region_proposal append)
-        self._h2_of, self._f32_missing = {}, set()      # planes are facts about THIS build's launches (buffers are reused across builds)
         net_conv = self._image_to_head(is_training)
         self._anchor_component()
         fused = self._fuse_tail_entry and not is_training and hasattr(self, "_fused_tail_entry")      # a method of resnetv1 only
@@ -709,15 +500,13 @@ class Network(object):
         return buf
 
     def graph_key(self, image_shape, im_info):
-        """Everything a captured TEST-mode chain depends on: network, image shape, im_info and every switch that changes a launch."""
+        """Everything a captured TEST-mode chain depends on: network, image shape, im_info, the configuration outside the plan, and the
+        plan the build of this shape would get (forward.Plan.key: every switch a route rule or a route reads)."""
         c = cfg[self._mode]
         return (self._tag, self._scope, self._num_classes, self._anchor_scales, self._anchor_ratios, bool(cfg.RESNET.MAX_POOL),
-                bool(cfg.USE_GPU_NMS), tuple(int(v) for v in image_shape), (float(im_info[0]), float(im_info[1])), self._mode, cfg.TEST.MODE, self._fuse_tail_entry,
-                c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH, cfg.TEST.RPN_TOP_N, cfg.POOLING_SIZE,
-                bool(cfg.HIP.WINOGRAD), int(cfg.HIP.WINOGRAD_MIN_CIN), int(cfg.HIP.WINOGRAD_M), tuple(cfg.HIP.WINOGRAD_F2_SCOPES),
-                tuple(cfg.HIP.WINOGRAD_DIRECT_SCOPES), bool(cfg.HIP.WINOGRAD_7X7), bool(cfg.HIP.FUSE_TAIL_MEAN), bool(cfg.HIP.MFMA_X3), bool(cfg.USE_E2E_TF),
-                bool(cfg.HIP.MFMA_H2), bool(cfg.HIP.H2_LAZY_SPLIT), int(cfg.HIP.H2_MIN_TILES), bool(cfg.HIP.H2_TRUNK_PLANES), int(cfg.HIP.H2_TILE_CFG), int(cfg.HIP.X3_TILE_CFG), bool(cfg.HIP.H2_TRAIN),
-                cfg.POOLING_MODE, int(cfg.HIP.ROI_ALIGN_SAMPLES))
+                bool(cfg.USE_GPU_NMS), tuple(int(v) for v in image_shape), (float(im_info[0]), float(im_info[1])), cfg.TEST.MODE, self._fuse_tail_entry,
+                c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH, cfg.TEST.RPN_TOP_N, cfg.POOLING_SIZE, bool(cfg.USE_E2E_TF),
+                cfg.POOLING_MODE, int(cfg.HIP.ROI_ALIGN_SAMPLES)) + forward.make_plan(self._mode, 0 if self._mode == "TRAIN" else image_shape[0], cfg.HIP).key()
 
     def shape_scope(self, sess, image_shape, im_info):
         """The buffer scope of one image shape of this network (frcnn_hip/runtime.py Session.shape_scope): at most cfg.HIP.GRAPH_CACHE_SHAPES
@@ -766,7 +555,6 @@ class Network(object):
             self._tape = []
             self._requires_grad = set()
             self._act_summaries = []
-            self._h2_of, self._f32_missing = {}, set()
             net_conv = self._image_to_head(False)
             self._anchor_component()
             rois = self._region_proposal(net_conv, False)
@@ -819,7 +607,6 @@ class Network(object):
         shape = (int(image.shape[0]), int(image.shape[1]), int(image.shape[2]), 4)
         with sess.shape_scope(("extract_head", self._tag, shape), group=("head", self._tag), cap=int(cfg.HIP.GRAPH_CACHE_SHAPES)):
             self._image = self._stage_image(sess, image)
-            self._h2_of, self._f32_missing = {}, set()
             ops.ws_scope = self._tag
             with self._plan_context(self, False):          # the same launch plan as forward_device: the same bits for the same image
                 feat = self._image_to_head(False)
@@ -1062,7 +849,7 @@ class Network(object):
         """cfg.HIP -> the solver handle's switches for the reverse sweep (frcnn_hip/train.py)."""
         train_op.winograd = ((int(cfg.HIP.WINOGRAD_M), int(cfg.HIP.WINOGRAD_MIN_CIN), bool(cfg.HIP.WINOGRAD_7X7))
                              if (cfg.HIP.WINOGRAD and cfg.HIP.WINOGRAD_TRAIN and cfg.HIP.WINOGRAD_DGRAD) else None)
-        train_op.h2_train = Network.h2_min_tiles("TRAIN") if (cfg.HIP.MFMA_H2 and cfg.HIP.H2_TRAIN) else None
+        train_op.h2_train = forward.h2_min_tiles("TRAIN", cfg.HIP) if (cfg.HIP.MFMA_H2 and cfg.HIP.H2_TRAIN) else None
         train_op.wgrad_stream = int(cfg.HIP.WGRAD_STREAM)
         train_op.wgrad_tn = bool(cfg.HIP.WGRAD_TN)
         train_op.prep_stream = bool(cfg.HIP.PREP_STREAM)

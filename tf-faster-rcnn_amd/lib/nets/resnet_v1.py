@@ -13,7 +13,7 @@ slim semantics restated (third-party):
   * blocks 1-3 form the stride-16 head (block3 stride 1), block4 (stride 1) runs per RoI on the
     7x7 crops followed by a spatial mean (resnet_v1.py:88-125).
 """
-from frcnn_hip import ACT_NONE, ACT_RELU, ops
+from frcnn_hip import ACT_NONE, ACT_RELU, forward, ops
 from model.config import cfg
 from nets.network import Network
 
@@ -90,26 +90,24 @@ class resnetv1(Network):
         M3 = N * ops.conv_out_size(H, 3, stride, pad[0], pad[1]) * ops.conv_out_size(W, 3, stride, pad[2], pad[3])
         if mean_rows and res_stride == 1 and stride == 1 and self._mean_fusable(M3, depth, base, prefix + "/conv3", mean_rows):
             r = self._conv(r, prefix + "/conv2", 3, stride, pad, act=ACT_RELU, bn_eps=BN_EPS, emit_h2=True, want_f32=False)
-            if self._h2_input(r) is not None:      # planes from conv2's output transform, or (direct conv2) a lazy split of its f32 result
-                return self._conv1x1_mean(r, prefix + "/conv3", mean_rows, act=ACT_RELU, bn_eps=BN_EPS, residual=shortcut)
+            if self._forms.planes_of(r) is not None:      # planes from conv2's output transform, or (direct conv2) a lazy split of its f32 result
+                return forward.conv1x1_mean(ops, self._sess, self._plan, self._forms, self._tag, prefix + "/conv3", r, mean_rows, ACT_RELU, BN_EPS, shortcut)
             # conv2 took the direct kernel (WINOGRAD_DIRECT_SCOPES / WINOGRAD_MIN_CIN) and H2_LAZY_SPLIT is off: no planes exist, so the
             # unfused pair -- conv3 on whatever pipe its float32 input allows, then the spatial mean
-            x = self._conv(r, prefix + "/conv3", 1, 1, act=ACT_RELU, bn_eps=BN_EPS, residual=shortcut, res_stride=1)
-            out = self._sess.buf(self._tag + "/fc7", (x.shape[0], x.shape[-1]))
-            return self._sess.mark("op:spatial_mean", 0, lambda: ops.spatial_mean(x, out=out), nbytes=4 * (x.numel() + out.numel()))
-        c3_h2 = res_stride == 1 and self._h2_eligible(M3, depth, base, 1, prefix + "/conv3")
+            return self._spatial_mean(self._conv(r, prefix + "/conv3", 1, 1, act=ACT_RELU, bn_eps=BN_EPS, residual=shortcut, res_stride=1))
+        c3_h2 = self._pointwise_route(prefix + "/conv3", M3, base, depth, res_stride) == "h2"
         r = self._conv(r, prefix + "/conv2", 3, stride, pad, act=ACT_RELU, bn_eps=BN_EPS, emit_h2=c3_h2, want_f32=not c3_h2)
         return self._conv(r, prefix + "/conv3", 1, 1, act=ACT_RELU, bn_eps=BN_EPS, residual=shortcut, res_stride=res_stride,
                           emit_h2=emit_out, want_f32=f32_out)
 
-    def _trunk_planes_only(self, rows, base, next_stride, next_prefix=None):
+    def _trunk_planes_only(self, rows, base, next_stride, next_prefix):
         """cfg.HIP.H2_TRUNK_PLANES: may a unit hand its output to the NEXT unit of the same block (identity shortcut) as operand
         planes only?  Yes when that unit's conv1 reads planes (h2-eligible), its conv3 takes the residual from planes (h2-eligible,
         stride 1) -- then nothing reads the float32 tensor.  The planes carry >= 22 significant bits (csrc/gemm_h2.hip)."""
         depth = 4 * base
-        return (bool(cfg.HIP.H2_TRUNK_PLANES) and next_stride == 1
-                and self._h2_eligible(rows, base, depth, 1, None if next_prefix is None else next_prefix + "/conv1")
-                and self._h2_eligible(rows, depth, base, 1, None if next_prefix is None else next_prefix + "/conv3"))
+        return (self._plan.h2_trunk_planes and next_stride == 1
+                and self._pointwise_route(next_prefix + "/conv1", rows, depth, base) == "h2"
+                and self._pointwise_route(next_prefix + "/conv3", rows, base, depth, next_stride) == "h2")
 
     def _run_blocks(self, x, blocks, emit_last=True):
         for bi, (name, base, n_units, stride) in enumerate(blocks):
@@ -134,7 +132,7 @@ class resnetv1(Network):
         N, H, W, C = net.shape
         out = self._sess.buf(self._tag + "/pool1", (N, ops.conv_out_size(H, 3, 2, 1, 1), ops.conv_out_size(W, 3, 2, 1, 1), C))
         self._sess.mark("op:maxpool", 0, lambda: ops.maxpool(net, 3, 2, (1, 1, 1, 1), out=out), nbytes=4 * (net.numel() + out.numel()))
-        return self._wrote(out)
+        return self._forms.wrote(out)
 
     def _image_to_head(self, is_training, reuse=None):
         assert (0 <= cfg.RESNET.FIXED_BLOCKS <= 3)
@@ -170,7 +168,7 @@ class resnetv1(Network):
         c1_out = sess.buf(self._tag + "/" + prefix + "/conv1_crop", (R, P, P, c1_map.shape[-1]))
         shortcut = self._crop_images(sc_map, rois, sc_out, bias=b_sc, act=ACT_NONE)
         r = self._crop_images(c1_map, rois, c1_out, bias=b_c1, act=ACT_RELU)
-        c3_h2 = self._h2_eligible(R * P * P, 4 * base, base, 1, prefix + "/conv3")
+        c3_h2 = self._pointwise_route(prefix + "/conv3", R * P * P, base, 4 * base, 1) == "h2"
         r = self._conv(r, prefix + "/conv2", 3, 1, (1, 1, 1, 1), act=ACT_RELU, bn_eps=BN_EPS, emit_h2=c3_h2, want_f32=not c3_h2)
         x = self._conv(r, prefix + "/conv3", 1, 1, act=ACT_RELU, bn_eps=BN_EPS, residual=shortcut, res_stride=1, emit_h2=n_units >= 2,
                        want_f32=not (n_units >= 2 and self._trunk_planes_only(R * P * P, base, stride if n_units == 2 else 1,
@@ -181,10 +179,7 @@ class resnetv1(Network):
                                  mean_rows=P * P if (fused and u == n_units) else 0, emit_out=u < n_units,
                                  f32_out=not (u < n_units and self._trunk_planes_only(R * P * P, base, stride if u + 1 == n_units else 1,
                                                                                       "%s/%s/unit_%d/bottleneck_v1" % (self._scope, name, u + 1))))
-        if fused:
-            return x                                          # [R, 2048]: the mean came out of the last conv3's epilogue
-        out = sess.buf(self._tag + "/fc7", (x.shape[0], x.shape[-1]))
-        return sess.mark("op:spatial_mean", 0, lambda: ops.spatial_mean(x, out=out), nbytes=4 * (x.numel() + out.numel()))
+        return x if fused else self._spatial_mean(x)              # fused: [R, 2048], the mean came out of the last conv3's epilogue
 
     def _head_to_tail(self, pool5, is_training, reuse=None):
         name, base, n_units, stride = self._blocks[-1]
@@ -195,15 +190,7 @@ class resnetv1(Network):
             for u in range(1, n_units + 1):
                 x = self._bottleneck(x, "%s/%s/unit_%d/bottleneck_v1" % (self._scope, name, u), base, 1, mean_rows=hw if u == n_units else 0)
             return x
-        fc7 = self._run_blocks(pool5, self._blocks[-1:], emit_last=False)
-        # average pooling done by reduce_mean (resnet_v1.py:124)
-        out = self._sess.buf(self._tag + "/fc7", (fc7.shape[0], fc7.shape[-1]))
-        res = self._sess.mark("op:spatial_mean", 0, lambda: ops.spatial_mean(fc7, out=out), nbytes=4 * (fc7.numel() + out.numel()))
-        if self._mode == "TRAIN":
-            self._tape.append(dict(kind="mean", x=fc7, y=res, name=self._scope + "/fc7_mean"))
-            if fc7.data_ptr() in self._requires_grad:
-                self._requires_grad.add(res.data_ptr())
-        return res
+        return self._spatial_mean(self._run_blocks(pool5, self._blocks[-1:], emit_last=False))      # reduce_mean (resnet_v1.py:124)
 
     def trainable_scope(self, scope):
         """resnet_v1.py:88-113: conv1 and the first cfg.RESNET.FIXED_BLOCKS blocks are frozen; everything else trains

@@ -73,10 +73,7 @@ class vgg16(Network):
         seed = (int(self._sample_seed) << 8) | int(layer)
         out = self._sess.buf(self._tag + "/dropout%d" % layer, tuple(x.shape))
         self._sess.mark("op:dropout", 0, lambda: ops.dropout(x, seed, 0.5, out=out, step_mult=256), nbytes=8 * x.numel())
-        self._tape.append(dict(kind="dropout", x=x, y=out, seed=seed, keep=0.5, name="dropout%d" % layer))
-        if x.data_ptr() in self._requires_grad:
-            self._requires_grad.add(out.data_ptr())
-        return out
+        return self._record("dropout", out, (x,), x=x, seed=seed, keep=0.5, name="dropout%d" % layer)
 
     def _head_to_tail(self, pool5, is_training, reuse=None):
         # slim.flatten is NHWC order, so fc6's [25088,4096] matrix is a 1x1 filter over the flattened [R,7*7*512] crops (the k order

@@ -602,6 +602,31 @@ int frcnn_proposal_target_layer_inject(const float* rpn_rois_d, const float* rpn
                                        int num_classes, int batch_size, const int* keep_inds_d, int n_fg, const double* means4,
                                        const double* stds4, const double* opts, float* rois_d, float* roi_scores_d, float* labels_d,
                                        float* bbox_targets_d, float* inside_w_d, float* outside_w_d, void* stream);
+/* Online hard example mining (Shrivastava et al. 2016; csrc/ohem_math.h states the rule): the target layer's outputs for the batch_size
+ * proposals with the largest loss under the CURRENT weights instead of a random sample.  rpn_rois_d [max_rois,5] / rpn_scores_d [max_rois]
+ * the padded proposal buffer with *num_rois_d valid rows (max_rois <= 3072, batch_size <= 3072); cls_score_d [max_rois,num_classes] /
+ * bbox_pred_d [max_rois,4*num_classes] a read-only forward of the RoI tail over those rows (TRAIN-mode predictions: no
+ * BBOX_NORMALIZE affine).  Every valid row is labelled as proposal_target_layer.py does before it samples (thresholds, means4 / stds4 /
+ * opts as above; opts[0] = TRAIN.USE_GT is refused), scored with its cross entropy plus, for a foreground row, its SmoothL1 (sigma 1)
+ * term -- in double, rounded once --, ordered by (loss descending, row ascending; a non-finite loss first), thinned by greedy NMS on the
+ * RoI boxes (nms_rule FRCNN_NMS_RULE_*, nms_thresh <= 0: no NMS, > 1: FRCNN_E_ARG), and the first batch_size kept rows are selected; too
+ * few kept rows are followed by suppressed ones in loss order, too few candidates repeat.  Outputs: the seven of the target layer (fg rows
+ * first; counts_d[4] = {fg selected, bg selected, fg candidates, bg candidates}), keep_inds_d [batch_size] int32 = the selected proposal
+ * rows (-1 where there was no candidate at all: those output rows are zero), roi_loss_d [max_rois] = the loss of every candidate, 0
+ * elsewhere.  One stream, the caller's workspace, no allocation, no host synchronisation; the same bits on every run.  The host entry
+ * computes the same bits from host pointers. */
+size_t frcnn_ohem_workspace_bytes(int max_rois, int num_classes);
+int frcnn_ohem_select(const float* rpn_rois_d, const float* rpn_scores_d, int max_rois, const int* num_rois_d, const float* gt_boxes_d,
+                      int G, int num_classes, const float* cls_score_d, const float* bbox_pred_d, int batch_size, double fg_thresh,
+                      double bg_thresh_hi, double bg_thresh_lo, const double* means4, const double* stds4, const double* opts,
+                      double nms_thresh, int nms_rule, float* rois_d, float* roi_scores_d, float* labels_d, float* bbox_targets_d,
+                      float* inside_w_d, float* outside_w_d, int* counts_d, int* keep_inds_d, float* roi_loss_d, void* ws,
+                      size_t ws_bytes, void* stream);
+int frcnn_ohem_select_host(const float* rpn_rois, const float* rpn_scores, int max_rois, const int* num_rois, const float* gt_boxes,
+                           int G, int num_classes, const float* cls_score, const float* bbox_pred, int batch_size, double fg_thresh,
+                           double bg_thresh_hi, double bg_thresh_lo, const double* means4, const double* stds4, const double* opts,
+                           double nms_thresh, int nms_rule, float* rois, float* roi_scores, float* labels, float* bbox_targets,
+                           float* inside_w, float* outside_w, int* counts, int* keep_inds, float* roi_loss);
 /* Losses of lib/nets/network.py:264-321, value + gradient w.r.t. the logits / predictions in one call.
  * softmax CE: logits [R,C] rows (rpn_A = 0) or the RPN pair layout (rpn_A = A: logits [H*W,2A], element
  * r = (a*H+h)*W+w pairs channels (a, A+a), labels_d in the [1,1,A*H,W] layout); label < 0 is ignored;

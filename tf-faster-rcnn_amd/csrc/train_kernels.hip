@@ -10,6 +10,7 @@
 // assignments, regression targets, weights) is bit-/1e-6-comparable with the oracle, and tests check
 // exactly that plus the counts.
 #include "common.h"
+#include "ohem_math.h"
 
 __device__ __forceinline__ u64 hash_key(u64 seed, u32 idx) {       // splitmix64 finaliser
   u64 z = seed + 0x9E3779B97F4A7C15ull * ((u64)idx + 1ull);
@@ -19,19 +20,8 @@ __device__ __forceinline__ u64 hash_key(u64 seed, u32 idx) {       // splitmix64
   return (z & ~0xFFFFFFFFull) | idx;                               // unique per index; never ~0
 }
 
-__device__ __forceinline__ double iou_f64(const float4 b, const float* __restrict__ q) {   // utils/bbox.pyx:28-54
-  const double b0 = b.x, b1 = b.y, b2 = b.z, b3 = b.w;
-  const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-  const double box_area = (q2 - q0 + 1) * (q3 - q1 + 1);
-  const double iw = (b2 < q2 ? b2 : q2) - (b0 > q0 ? b0 : q0) + 1;
-  if (iw > 0) {
-    const double ih = (b3 < q3 ? b3 : q3) - (b1 > q1 ? b1 : q1) + 1;
-    if (ih > 0) {
-      const double ua = (b2 - b0 + 1) * (b3 - b1 + 1) + box_area - iw * ih;
-      return iw * ih / ua;
-    }
-  }
-  return 0.0;
+__device__ __forceinline__ double iou_f64(const float4 b, const float* __restrict__ q) {   // utils/bbox.pyx:28-54, stated in csrc/ohem_math.h
+  return ohem_iou_f64(b.x, b.y, b.z, b.w, q);
 }
 
 // bbox_transform for one pair (model/bbox_transform.py:14-32), f32 like the numpy call with f32 inputs

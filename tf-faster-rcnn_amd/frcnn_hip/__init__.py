@@ -141,6 +141,11 @@ SIGNATURES = {
                                             c_longlong, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "frcnn_proposal_target_layer_dn": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_double, c_double, c_double, c_double, _P, _P,
                                                c_longlong, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "frcnn_ohem_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "frcnn_ohem_select": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, _P, c_int, c_double, c_double, c_double, _P, _P, _P, c_double, c_int,
+                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "frcnn_ohem_select_host": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, _P, c_int, c_double, c_double, c_double, _P, _P, _P, c_double,
+                                       c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "frcnn_loss_workspace_bytes": (c_size_t, [c_longlong]),
     "frcnn_softmax_ce_loss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "frcnn_smooth_l1_loss": (c_int, [_P, _P, _P, _P, c_longlong, c_float, c_float, _P, _P, _P, c_size_t, _P]),

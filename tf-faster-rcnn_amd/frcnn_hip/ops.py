@@ -1275,6 +1275,55 @@ def proposal_target_layer(rpn_rois, rpn_scores, gt_boxes, num_classes, batch_siz
     return rois, sc, labels, tg, iw, ow, counts
 
 
+def ohem_select(rpn_rois, rpn_scores, num, gt_boxes, num_classes, cls_score, bbox_pred, batch_size=256, fg_thresh=0.5, bg_hi=0.5, bg_lo=0.0,
+                means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2), opts=None, nms_thresh=0.7, rule=NMS_RULE_CPU):
+    """Online hard example mining on the device (frcnn_ohem_select, csrc/ohem_math.h): the padded proposal buffer rpn_rois [N,5] /
+    rpn_scores [N] with num (int32 [1], device) valid rows, and cls_score [N,C] / bbox_pred [N,4C] of a read-only pass over those rows
+    -> (rois [B,5], scores [B], labels [B,1], targets, inside, outside [B,4C], counts int32 [4], keep_inds int32 [B], roi_loss [N])."""
+    _chk(rpn_rois), _chk(rpn_scores), _chk(gt_boxes), _chk(cls_score), _chk(bbox_pred), _chk(num, torch.int32)
+    dev, N, G, B, C = rpn_rois.device, rpn_rois.shape[0], gt_boxes.shape[0], int(batch_size), int(num_classes)
+    if tuple(cls_score.shape) != (N, C) or tuple(bbox_pred.shape) != (N, 4 * C) or rpn_scores.numel() != N:
+        raise ValueError("ohem_select: cls_score / bbox_pred / rpn_scores must have one row per row of rpn_rois")
+    rois = _empty((B, 5), dtype=torch.float32, device=dev)
+    sc = _empty((B,), dtype=torch.float32, device=dev)
+    labels = _empty((B, 1), dtype=torch.float32, device=dev)
+    tg, iw, ow = (_empty((B, 4 * C), dtype=torch.float32, device=dev) for _ in range(3))
+    counts = _empty((4,), dtype=torch.int32, device=dev)
+    keep = _empty((B,), dtype=torch.int32, device=dev)
+    loss = _empty((N,), dtype=torch.float32, device=dev)
+    ws = workspace(lib().frcnn_ohem_workspace_bytes(N, C), dev, "ohem")
+    m, s, o = _host_doubles(means), _host_doubles(stds), (_host_doubles(opts) if opts is not None else (None, None))
+    call("frcnn_ohem_select", _ptr(rpn_rois), _ptr(rpn_scores), N, _ptr(num), _ptr(gt_boxes), G, C, _ptr(cls_score), _ptr(bbox_pred), B,
+         float(fg_thresh), float(bg_hi), float(bg_lo), m[1], s[1], o[1], float(nms_thresh), int(rule), _ptr(rois), _ptr(sc), _ptr(labels),
+         _ptr(tg), _ptr(iw), _ptr(ow), _ptr(counts), _ptr(keep), _ptr(loss), _ptr(ws), ws.numel(), _stream())
+    if _binding.recorder is not None:
+        _binding.recorder.patch_last(5, var="gt")    # the image's box count (gt_boxes: the first G rows of a static buffer)
+    return rois, sc, labels, tg, iw, ow, counts, keep, loss
+
+
+def ohem_select_host(rpn_rois, rpn_scores, num, gt_boxes, num_classes, cls_score, bbox_pred, batch_size=256, fg_thresh=0.5, bg_hi=0.5,
+                     bg_lo=0.0, means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2), opts=None, nms_thresh=0.7, rule=NMS_RULE_CPU):
+    """frcnn_ohem_select_host: the same on HOST numpy arrays, no GPU needed; num an int.  -> the same nine results as numpy arrays."""
+    f32 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
+    C, B = int(num_classes), int(batch_size)
+    rpn_rois = f32(rpn_rois, (-1, 5))
+    N = rpn_rois.shape[0]
+    rpn_scores, gt_boxes, cls_score, bbox_pred = f32(rpn_scores, (N,)), f32(gt_boxes, (-1, 5)), f32(cls_score, (N, C)), f32(bbox_pred, (N, 4 * C))
+    nb = max(B, 1)
+    rois, sc, labels = np.zeros((nb, 5), np.float32), np.zeros(nb, np.float32), np.zeros((nb, 1), np.float32)
+    tg, iw, ow = (np.zeros((nb, 4 * C), np.float32) for _ in range(3))
+    counts, keep, loss = np.zeros(4, np.int32), np.zeros(nb, np.int32), np.zeros(max(N, 1), np.float32)
+    n = np.array([int(num)], dtype=np.int32)
+    m, s = np.ascontiguousarray(means, dtype=np.float64), np.ascontiguousarray(stds, dtype=np.float64)
+    o = None if opts is None else np.ascontiguousarray(opts, dtype=np.float64)
+    check(lib().frcnn_ohem_select_host(rpn_rois.ctypes.data, rpn_scores.ctypes.data, N, n.ctypes.data, gt_boxes.ctypes.data, gt_boxes.shape[0], C,
+                                       cls_score.ctypes.data, bbox_pred.ctypes.data, B, float(fg_thresh), float(bg_hi), float(bg_lo),
+                                       m.ctypes.data, s.ctypes.data, None if o is None else o.ctypes.data, float(nms_thresh), int(rule),
+                                       rois.ctypes.data, sc.ctypes.data, labels.ctypes.data, tg.ctypes.data, iw.ctypes.data, ow.ctypes.data,
+                                       counts.ctypes.data, keep.ctypes.data, loss.ctypes.data), "frcnn_ohem_select_host")
+    return rois, sc, labels, tg, iw, ow, counts, keep, loss
+
+
 def softmax_ce_loss(logits, labels, rpn_shape=None):
     """-> (loss [1], dlogits like logits).  rpn_shape=(A,H,W): logits [1,H,W,2A] with labels [1,1,A*H,W]."""
     _chk(logits), _chk(labels)

@@ -158,6 +158,13 @@ __C = AttrDict(
     # csrc/roialign_math.h): every POOLING_SIZE x POOLING_SIZE bin is the mean of S x S bilinear samples, S in 1..4 and fixed (no adaptive
     # ceil(roi / P) count).  Only read when POOLING_MODE is 'align'; 'crop' (tf.image.crop_and_resize, the reference's only mode) stays the
     # default and exactly the launches it always made.  Part of the graph key.  Cost next to the crop: profiles/roi_align.txt.
+    # OHEM: online hard example mining (Shrivastava et al. 2016; csrc/ohem_math.h, frcnn_ohem_select) in the training step: a read-only
+    # forward of the RoI tail scores ALL TRAIN.RPN_POST_NMS_TOP_N proposals (at most 3072) with the current weights, and the step trains on
+    # the TRAIN.BATCH_SIZE proposals with the largest loss -- after a greedy NMS on the RoI boxes at OHEM_NMS_THRESH (<= 0: no NMS; at
+    # most 1; the rule cfg.USE_GPU_NMS selects) -- instead of proposal_target_layer's random sample: TRAIN.FG_FRACTION is not read,
+    # FG_THRESH / BG_THRESH_HI / BG_THRESH_LO still say which proposals are foreground, background or neither.  TRAIN.USE_GT is refused with
+    # it.  Selected on the device, so TRAIN_REPLAY stays; part of the recorded-step key like every HIP key.  False, the default: exactly the
+    # launches the step always made.  Cost (about one more tail forward over all proposals): profiles/ohem.txt.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
@@ -165,7 +172,7 @@ __C = AttrDict(
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
              GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1,
              SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001, TEST_FLIP=False, BBOX_VOTE=False, BBOX_VOTE_THRESH=0.8,
-             ROI_ALIGN_SAMPLES=2))
+             ROI_ALIGN_SAMPLES=2, OHEM=False, OHEM_NMS_THRESH=0.7))
 
 
 def pooling_description(c=None):
@@ -174,6 +181,15 @@ def pooling_description(c=None):
     if c.POOLING_MODE == 'align':
         return "RoI pooling: align (RoIAlign, %d x %d samples per bin)" % (c.HIP.ROI_ALIGN_SAMPLES, c.HIP.ROI_ALIGN_SAMPLES)
     return "RoI pooling: %s" % (c.POOLING_MODE,)
+
+
+def ohem_description(c=None):
+    """One line for the training tool's log when cfg.HIP.OHEM is on (None otherwise)."""
+    c = __C if c is None else c
+    if not c.HIP.OHEM:
+        return None
+    nms = "NMS at %g" % c.HIP.OHEM_NMS_THRESH if float(c.HIP.OHEM_NMS_THRESH) > 0 else "no NMS"
+    return "RoI minibatch: online hard example mining, the %d hardest of %d proposals (%s)" % (c.TRAIN.BATCH_SIZE, c.TRAIN.RPN_POST_NMS_TOP_N, nms)
 
 
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))

@@ -44,6 +44,8 @@ class Network(object):
         self._train_state = None               # the solver handle of the last train_step_with_summary (get_summary's regulariser term)
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
         self._plan, self._forms = None, None   # the last graph build's forward.Plan and forward.Forms (_plan_context)
+        self._read_only = False                # inside _ohem_scores: launches as in TRAIN mode, nothing goes on the tape
+        self._ohem = {}                        # cfg.HIP.OHEM: keep_inds, roi_loss and the read-only pass's cls_score / bbox_pred of the last step
 
     # ------------------------------------------------------------------ variable declaration
     def _var(self, name, shape, init, arg=None):
@@ -89,7 +91,7 @@ class Network(object):
     def _record(self, kind, y, sources, **fields):
         """TRAIN mode: the tape record of the launches that wrote y; y takes a gradient when one of its sources does, or when the record
         names a filter (`scope`) the solver updates."""
-        if self._mode == "TRAIN":
+        if self._mode == "TRAIN" and not self._read_only:
             self._tape.append(dict(fields, kind=kind, y=y))
             if ("scope" in fields and self.trainable_scope(fields["scope"])) or any(s is not None and s.data_ptr() in self._requires_grad for s in sources):
                 self._requires_grad.add(y.data_ptr())
@@ -252,6 +254,42 @@ class Network(object):
         self._num_rois = None
         return rois, roi_scores
 
+    def _ohem_scores(self, net_conv, rois):
+        """cfg.HIP.OHEM: cls_score [N,C] / bbox_pred [N,4C] of ALL N rows of the padded proposal buffer under the current weights -- pool5,
+        _head_to_tail (without dropout) and _region_classification with the training pass's plan and routes, as a READ-ONLY pass: nothing
+        goes on the tape, its activations live under the tag suffix "/ohem" (Session.buf keys by name and shape: with N == BATCH_SIZE the
+        training pass would otherwise write the same buffers), and _predictions / _layers are left for the training pass to write.  Batch
+        norm is frozen, so this is the arithmetic of the training forward.  Derived filters (operand planes, Winograd U) come from the
+        session's caches and PreparedFilters like everybody's, so they follow the solver."""
+        tag, preds, layers = self._tag, dict(self._predictions), dict(self._layers)
+        self._tag, self._forms.tag, self._read_only = tag + "/ohem", tag + "/ohem", True
+        try:
+            pool5 = self._crop_pool_layer(net_conv, rois, "pool5")
+            fc7 = self._head_to_tail(pool5, False)
+            self._region_classification(fc7, False)
+            return self._predictions["cls_score"], self._predictions["bbox_pred"]
+        finally:
+            self._tag, self._forms.tag, self._read_only = tag, tag, False
+            self._predictions, self._layers = preds, layers
+
+    def _ohem_target_layer(self, net_conv, rois, roi_scores, name):
+        """cfg.HIP.OHEM instead of _proposal_target_layer: the BATCH_SIZE proposals with the largest loss (csrc/ohem_math.h)"""
+        t = cfg.TRAIN
+        cls_score, bbox_pred = self._ohem_scores(net_conv, rois)
+        out = ops.ohem_select(rois, roi_scores.view(-1), self._num_rois, self._gt_boxes, self._num_classes, cls_score, bbox_pred,
+                              t.BATCH_SIZE, t.FG_THRESH, t.BG_THRESH_HI, t.BG_THRESH_LO, t.BBOX_NORMALIZE_MEANS, t.BBOX_NORMALIZE_STDS,
+                              opts=ops.roi_target_opts(t.USE_GT, t.BBOX_INSIDE_WEIGHTS), nms_thresh=float(cfg.HIP.OHEM_NMS_THRESH),
+                              rule=self._nms_rule())
+        proposals, proposal_scores, num = rois, roi_scores, self._num_rois
+        rois, roi_scores, labels, tg, iw, ow, counts, keep, loss = out
+        rois = ops.t_copy(self._sess.buf(self._tag + "/" + name + "/rois", tuple(rois.shape)), rois)      # (as _proposal_target_layer)
+        self._proposal_targets = dict(rois=rois, labels=labels, bbox_targets=tg, bbox_inside_weights=iw, bbox_outside_weights=ow,
+                                      counts=counts)
+        self._ohem = dict(keep_inds=keep, roi_loss=loss, cls_score=cls_score, bbox_pred=bbox_pred, proposals=proposals,
+                          proposal_scores=proposal_scores, num_rois=num)
+        self._num_rois = None
+        return rois, roi_scores
+
     def _smooth_l1_loss(self, bbox_pred, bbox_targets, bbox_inside_weights, bbox_outside_weights, sigma=1.0, dim=[1]):
         """network.py:264-277 -> (loss [1], d loss / d bbox_pred).  dim=[1]: mean over rows; dim=[1,2,3]: batch of 1."""
         div = float(bbox_pred.shape[0]) if list(dim) == [1] else 1.0
@@ -333,7 +371,10 @@ class Network(object):
         if is_training:                                                                                    # :338-343
             rois, roi_scores = self._proposal_layer(rpn_cls_prob, rpn_bbox_pred, "rois")
             self._anchor_target_layer(rpn_cls_score, "anchor")
-            rois, _ = self._proposal_target_layer(rois, roi_scores, "rpn_rois")
+            if cfg.HIP.OHEM:
+                rois, _ = self._ohem_target_layer(net_conv, rois, roi_scores, "rpn_rois")
+            else:
+                rois, _ = self._proposal_target_layer(rois, roi_scores, "rpn_rois")
         elif cfg.TEST.MODE == "nms":
             rois, _ = self._proposal_layer(rpn_cls_prob, rpn_bbox_pred, "rois")
         elif cfg.TEST.MODE == "top":
@@ -437,11 +478,20 @@ class Network(object):
             bad.append("HIP.SOFT_NMS_MIN_SCORE = %r (must be >= 0)" % (h.SOFT_NMS_MIN_SCORE,))
         if not 0.0 < float(h.BBOX_VOTE_THRESH) <= 1.0:
             bad.append("HIP.BBOX_VOTE_THRESH = %r (must be in (0, 1])" % (h.BBOX_VOTE_THRESH,))
+        if h.OHEM:
+            if not float(h.OHEM_NMS_THRESH) <= 1.0:
+                bad.append("HIP.OHEM_NMS_THRESH = %r (at most 1; <= 0 skips the NMS)" % (h.OHEM_NMS_THRESH,))
+            if t.USE_GT:
+                bad.append("TRAIN.USE_GT = True with HIP.OHEM (the candidates are the proposal rows of the read-only pass)")
+            if int(t.RPN_POST_NMS_TOP_N) > Network.OHEM_MAX_ROWS or int(t.BATCH_SIZE) > Network.OHEM_MAX_ROWS:
+                bad.append("HIP.OHEM with TRAIN.RPN_POST_NMS_TOP_N = %d, TRAIN.BATCH_SIZE = %d (frcnn_ohem_select holds at most %d rows)"
+                           % (int(t.RPN_POST_NMS_TOP_N), int(t.BATCH_SIZE), Network.OHEM_MAX_ROWS))
         if h.TEST_FLIP and mode == "TEST":
             bad += Network._flip_refusals()
         if bad:
             raise NotImplementedError("unsupported configuration for the HIP path: " + "; ".join(bad))
 
+    OHEM_MAX_ROWS = 3072                  # OHEM_MAXN of csrc/ohem_math.h: proposal rows, and rows of the batch
     FLIP_MAX_ROWS = 1024                  # rows per image and class the post-processing holds (frcnn_detect_post_*: R <= 1024)
 
     @staticmethod

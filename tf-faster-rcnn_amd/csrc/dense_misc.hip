@@ -8,6 +8,15 @@ extern "C" const char* frcnn_build_info(void) { return "libfrcnn_hip gfx950 (CDN
 // ---- max pool (nets/resnet_v1.py:83-84 pool1: pad 1 + 3x3/2 VALID; nets/vgg16.py:30-39 2x2/2 SAME;
 //      nets/network.py:157).  Out-of-image taps are skipped, which equals TF's SAME behaviour and,
 //      for the post-ReLU ResNet stem, the explicit zero pad.  ZERO_PAD makes the zero explicit.
+//      NaN rule (common.h, "Activations that KEEP NaN"): an output is NaN iff an in-image tap of its window is NaN.  fmaxf alone drops
+//      NaN, so the running maximum is sticky; NaN-free operands still go through fmaxf and keep its bits.  The zero clamp is act_relu's form.
+__device__ __forceinline__ float pool_max(float m, float v) {
+  const float r = fmaxf(m, v);
+  return v != v ? v : (m != m ? m : r);
+}
+__device__ __forceinline__ float4 pool_max(float4 m, float4 v) {
+  return make_float4(pool_max(m.x, v.x), pool_max(m.y, v.y), pool_max(m.z, v.z), pool_max(m.w, v.w));
+}
 template <bool ZERO_PAD>
 __global__ void k_maxpool(const float4* __restrict__ x, int N, int H, int W, int C4, int k, int stride, int pt, int pl,
                           float4* __restrict__ y, int OH, int OW) {
@@ -27,13 +36,13 @@ __global__ void k_maxpool(const float4* __restrict__ x, int N, int H, int W, int
       const int iw = ow * stride - pl + dx;
       if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
         const float4 v = x[((size_t)(img * H + ih) * W + iw) * C4 + c4];
-        m = make_float4(fmaxf(m.x, v.x), fmaxf(m.y, v.y), fmaxf(m.z, v.z), fmaxf(m.w, v.w));
+        m = pool_max(m, v);
       } else {
         any_oob = true;
       }
     }
   }
-  if (ZERO_PAD && any_oob) m = make_float4(fmaxf(m.x, 0.f), fmaxf(m.y, 0.f), fmaxf(m.z, 0.f), fmaxf(m.w, 0.f));
+  if (ZERO_PAD && any_oob) m = act_relu(m);
   y[t] = m;
 }
 

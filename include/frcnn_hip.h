@@ -61,6 +61,11 @@ size_t frcnn_nms_workspace_bytes(int max_boxes);
  * keep_d [max_keep] int32 receives kept ORIGINAL indices in descending-score order
  * (ties: lower index first), num_keep_d the count (<= max_keep; the greedy scan stops there, which
  * equals truncating the full keep list, lib/layer_utils/proposal_layer.py:44-45).
+ * Order of scores, here and in every sort, top-K and score cut of this library (proposal layers, frcnn_non_max_suppression,
+ * frcnn_detect_post*): descending value, lower index first among equals.  -0.0 and +0.0 are EQUAL (the index decides, as in numpy's
+ * argsort); every NaN ranks ABOVE +inf (numpy's `argsort()[::-1]` puts NaN first) and all NaNs are equal, whatever their sign or
+ * payload.  A score that is written out keeps its input bits, a zero's sign included; a NaN is written as a quiet NaN.  The per-class
+ * stage of frcnn_detect_post* drops NaN scores with the rows at or below score_thresh (`scores > thresh`, lib/model/test.py:163).
  * frcnn_nms: rule FRCNN_NMS_RULE_CPU -- suppress iff (double)ovr >= thresh, exactly as lib/nms/cpu_nms.c:2239-2241.
  * frcnn_nms_rule: the rule is an argument (FRCNN_NMS_RULE_GPU = what gpu_nms / the CUDA kernel compute).  k <= 65536. */
 int frcnn_nms(const float* dets_d, int k, double thresh, int max_keep, int* keep_d, int* num_keep_d,

@@ -134,8 +134,13 @@ def clip_boxes_final(boxes, im_shape):
 
 # ----------------------------------------------------------------------------- NMS / IoU (C)
 def order_desc(scores):
-    """(score desc, index asc): the deterministic stand-in for `scores.argsort()[::-1]`."""
-    return np.argsort(-scores.astype(np.float64), kind="stable")
+    """(score desc, index asc): the deterministic stand-in for `scores.argsort()[::-1]`.  -0.0 and +0.0 are equal (the index
+    decides); every NaN ranks above +inf, as in `argsort()[::-1]` (numpy sorts NaN to the end ascending), and all NaNs are equal
+    whatever their sign or payload.  NaN-free input: exactly the stable argsort of the negated scores."""
+    s = np.asarray(scores).astype(np.float64)
+    order = np.argsort(-s, kind="stable")                              # NaN last, in index order (a stable sort)
+    nan = np.isnan(s[order])
+    return np.concatenate([order[nan], order[~nan]]) if nan.any() else order
 
 
 def cpu_nms(dets, thresh):

@@ -8,17 +8,10 @@ import torch
 import frcnn_oracle as ora
 import gen_golden_ref_gpu_nms as gen_ref
 import synth
+from score_cases import box_tol          # 2 ulp of the coordinate, per element (shared with tests/test_select_gpu.py)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def box_tol(want):
-    """2 ulp of the coordinate (assert what is measured), per element.  A decoded coordinate is pcx -+ 0.5 * pw
-    (bbox_transform.py:58-65) evaluated at the magnitude of its TERMS, so coordinates below 512 px are held to 2 ulp at 512 px
-    (1.22e-4 px); device expf vs np.exp is what differs, the measured maxima are 1 ulp (6.1e-5 px below 1024 px, 1.22e-4 px above)."""
-    mag = np.maximum(np.abs(np.asarray(want, dtype=np.float32)), np.float32(512.0))
-    return 2.0 * np.spacing(mag).astype(np.float64)
 
 
 BOX_TOL = float(box_tol(np.float32(1000.0)))            # scalar form for printouts: 1.22e-4 px

@@ -70,15 +70,23 @@ static inline float thresh_to_f32(double thresh) {
   return f;
 }
 
-// Monotone float -> uint32 map (larger float <=> larger uint).
+// Order of scores, stated once (DESIGN.md "Order of scores"): descending value, index ascending among equals; -0.0 and +0.0 are EQUAL
+// (as in numpy's argsort, so the index decides between them); every NaN ranks above +inf (numpy's `argsort()[::-1]` puts NaN first) and
+// all NaNs are equal -- sign and payload play no part.
+// float -> uint32 map, monotone in that order: larger score <=> larger uint, equal scores <=> equal uints.
 __device__ __forceinline__ u32 sortable_u32(float f) {
   u32 b = __float_as_uint(f);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;          // NaN, either sign, any payload
+  if (b == 0x80000000u) b = 0u;                                     // -0.0 compares as +0.0
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-// 64-bit sort key: (score descending, index ascending) <=> key descending.  Keys are unique.
+// 64-bit sort key: (score descending, index ascending) <=> key descending.  Keys are unique: the index (< 2^31) sits in bits 1..31.
+// Bit 0 carries the sign of a zero score, which sortable_u32 drops; it lies BELOW the unique index, so it never decides a comparison.
 __device__ __forceinline__ u64 make_key(float score, u32 index) {
-  return ((u64)sortable_u32(score) << 32) | (u64)(0xffffffffu - index);
+  const u32 negzero = __float_as_uint(score) == 0x80000000u ? 1u : 0u;
+  return ((u64)sortable_u32(score) << 32) | (u64)(((0x7fffffffu - index) << 1) | negzero);
 }
+__device__ __forceinline__ u32 key_index(u64 key) { return 0x7fffffffu - ((u32)key >> 1); }
 
 // a if a >= b else b  /  a if a <= b else b   (lib/nms/cpu_nms.pyx:11-15)
 __device__ __forceinline__ float rmax(float a, float b) { return a >= b ? a : b; }
@@ -139,9 +147,16 @@ __device__ __forceinline__ float4 decode_box(const float4 b, const float4 d) {
   return make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
 }
 
-// inverse of sortable_u32 (exact: the score comes back bit for bit out of a sort key)
+// inverse of sortable_u32 for every score but a zero and a NaN (which share their uint with other bit patterns)
 __device__ __forceinline__ float unsortable_f32(u32 k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// the score of a make_key key: the input's bits, a zero's sign included; a NaN comes back as the quiet NaN 0x7fc00000
+__device__ __forceinline__ float key_score(u64 key) {
+  const u32 hi = (u32)(key >> 32);
+  if (hi == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+  if (hi == 0x80000000u) return __uint_as_float(((u32)key & 1u) << 31);
+  return unsortable_f32(hi);
 }
 // per-image slice of a batched scratch / tensor: base + b * stride_bytes
 template <typename T>

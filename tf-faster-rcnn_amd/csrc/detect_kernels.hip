@@ -116,7 +116,10 @@ __global__ void k_boxes_scores_key(const float4* __restrict__ in_boxes, const fl
 // (proposal_layer.py:34-38) needs the K = 6000 best candidates in order, not a sort of all N = 21 546 (63 000 at
 // 800x1333, A = 15).  One 1024-thread workgroup per image finds the K-th largest 64-bit key exactly by an 8-pass
 // radix select (keys are unique, so exactly K keys are >= it), then compacts those K keys (any order; stage 2b sorts
-// them) and zeroes their rank counters.  Reads 8N bytes nine times out of L2; replaces an O(N^2) counting sort
+// them) and zeroes their rank counters.  The uniqueness comes from the index half of the key alone (make_key, csrc/common.h): equal
+// scores -- a constant or saturated RPN map -- leave the last four passes (shift 24...0) to decide the cut, and more than SEL_LIST keys
+// in the cut's 16-bit bucket keep all eight passes on the global scan.  tests/test_select_gpu.py runs both on tied, saturated and
+// non-finite scores (oracle/score_cases.py).  Reads 8N bytes nine times out of L2; replaces an O(N^2) counting sort
 // over all anchors.
 // ------------------------------------------------------------------------------------------------
 // One radix-select step over a 256-bin histogram: the bin that holds the k-th largest key and the number of keys in the bins
@@ -279,7 +282,8 @@ __global__ __launch_bounds__(256) void k_rank(const u64* __restrict__ keys_all, 
   if (i < N && cnt) atomicAdd(&rank[i], cnt);
 }
 
-// stage 3: scatter the K selected candidates into score order.  The score is recovered bit for bit from the key.
+// stage 3: scatter the K selected candidates into score order.  The score is recovered bit for bit from the key (key_score: a zero
+// keeps its sign; a NaN comes back as the quiet NaN).
 __global__ void k_scatter_sorted(const float4* __restrict__ boxes_all, const u64* __restrict__ ckeys_all,
                                  const u32* __restrict__ rank_all, int K, float4* __restrict__ sboxes_all,
                                  float* __restrict__ sscores_all, int* __restrict__ sidx_all, size_t img) {
@@ -288,9 +292,9 @@ __global__ void k_scatter_sorted(const float4* __restrict__ boxes_all, const u64
   const int b = blockIdx.y;
   const u64 key = img_ptr(ckeys_all, img, b)[t];
   const u32 r = img_ptr(rank_all, img, b)[t];
-  const u32 n = 0xffffffffu - (u32)key;
+  const u32 n = key_index(key);
   img_ptr(sboxes_all, img, b)[r] = img_ptr(boxes_all, img, b)[n];
-  img_ptr(sscores_all, img, b)[r] = unsortable_f32((u32)(key >> 32));
+  img_ptr(sscores_all, img, b)[r] = key_score(key);
   img_ptr(sidx_all, img, b)[r] = (int)n;
 }
 
@@ -1316,7 +1320,7 @@ __global__ __launch_bounds__(PC_THREADS) void k_perclass_nms(const float* __rest
     for (int q = 0; q < R; ++q) rk += (keys[q] > mine) ? 1 : 0;
     if (rk < nv) {
       sboxes[rk] = boxes[r];
-      sscores[rk] = unsortable_f32((u32)(mine >> 32));
+      sscores[rk] = key_score(mine);
     }
   }
   __syncthreads();                                      // keys / boxes dead from here: the mask takes their place
@@ -1515,23 +1519,23 @@ __device__ __forceinline__ int soft_nms_wave(float4 (&box)[PL], float (&sc)[PL],
   float ar[PL];
   u32 bhi = 0, blo = 0;                                 // the lane's best live key; 0 = none (no finite score maps to 0)
   float4 bb = make_float4(0, 0, 0, 0);
-  float ba = 0.0f;
+  float ba = 0.0f, bs = 0.0f;                           // bs: the best slot's score itself (the key does not hold a zero's sign)
 #pragma unroll
   for (int i = 0; i < PL; ++i) {
     ar[i] = softnms_area(box[i].x, box[i].y, box[i].z, box[i].w);
     const u32 hi = softnms_sortable(sc[i]);
     if (((live >> i) & 1u) && hi > bhi) {               // slots ascend in r: `>` keeps the lower r of equal scores
-      bhi = hi, blo = ~(lane + 64u * i), bb = box[i], ba = ar[i];
+      bhi = hi, blo = ~(lane + 64u * i), bb = box[i], ba = ar[i], bs = sc[i];
     }
   }
   int m = 0;
   for (;;) {
     const u32 whi = wave_max_u32(bhi);
     if (whi == 0) break;                                // nothing left
-    const float wscore = softnms_unsortable(whi);
-    if (wscore < min_score) break;
     const u32 wr = ~wave_max_u32(bhi == whi ? blo : 0u);
     const int wl = __builtin_amdgcn_readfirstlane((int)(wr & 63u));
+    const float wscore = readlane_f32(bs, wl);
+    if (wscore < min_score) break;
     const float4 wb = make_float4(readlane_f32(bb.x, wl), readlane_f32(bb.y, wl), readlane_f32(bb.z, wl), readlane_f32(bb.w, wl));
     const float wa = readlane_f32(ba, wl);
     emit(m, wb, wscore, wr);
@@ -1546,7 +1550,7 @@ __device__ __forceinline__ int soft_nms_wave(float4 (&box)[PL], float (&sc)[PL],
         const float w = METHOD == SOFTNMS_LINEAR ? softnms_weight_linear(ov, thr, rule) : softnms_weight_gaussian(ov, sigma);
         sc[i] = sc[i] * w;
         const u32 hi = softnms_sortable(sc[i]);
-        if (hi > bhi) bhi = hi, blo = ~r, bb = box[i], ba = ar[i];
+        if (hi > bhi) bhi = hi, blo = ~r, bb = box[i], ba = ar[i], bs = sc[i];
       }
     }
   }

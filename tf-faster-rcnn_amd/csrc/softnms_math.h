@@ -41,12 +41,15 @@
 SOFTNMS_HD uint32_t softnms_f32_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 SOFTNMS_HD float softnms_bits_f32(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 
-// make_key(score, r) of csrc/common.h: (score descending, r ascending) <=> key descending; never 0 for a finite score
+// sortable_u32(score) of csrc/common.h and its order: (score descending, r ascending) <=> key descending; never 0 for a finite score;
+// -0.0 and +0.0 share one value (r decides between them), every NaN maps to 0xffffffff, above +inf.  The score that is written out is
+// read from where it is kept (cur[] here, the lane's registers on the device), never rebuilt from the key.
 SOFTNMS_HD uint32_t softnms_sortable(float f) {
-  const uint32_t b = softnms_f32_bits(f);
+  uint32_t b = softnms_f32_bits(f);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-SOFTNMS_HD float softnms_unsortable(uint32_t k) { return softnms_bits_f32((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 SOFTNMS_HD uint64_t softnms_key(float score, uint32_t r) { return ((uint64_t)softnms_sortable(score) << 32) | (uint64_t)(0xffffffffu - r); }
 
 SOFTNMS_HD float softnms_rmax(float a, float b) { return a >= b ? a : b; }

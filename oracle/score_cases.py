@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- the score vectors that reach the ordering machinery of csrc/detect_kernels.hip (make_key,
-k_select_topk, k_rank / k_scatter_sorted, the rank sort of k_perclass_nms, k_final_select) where oracle/synth.py's inputs do not:
+"""TEST INFRASTRUCTURE ONLY -- the score vectors that reach the ordering machinery of csrc/detect_kernels.hip and
+csrc/detect_post.hip (make_key, k_select_topk, k_rank / k_scatter_sorted, the rank sort of k_perclass_nms, k_final_select) where oracle/synth.py's inputs do not:
 synth makes every score unique (tie_free) and spreads them over (0, 1), so the K-th key is always decided by the score half alone,
 its 16-bit bucket always fits the LDS list, and no two rows ever tie at a cut.  Shared by tests/test_select_cpu.py (the numpy
 restatement oracle/select_ref.py and its planted mistakes) and tests/test_select_gpu.py (the kernels); stated once, here.

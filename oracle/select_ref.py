@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- the ordering machinery of csrc/detect_kernels.hip restated in plain numpy on uint64 keys, step by step
-as the kernels do it (NOT as a sort): key construction (make_key), the 8-pass radix select of k_select_topk with its LDS-list
+"""TEST INFRASTRUCTURE ONLY -- the ordering machinery of csrc/detect_kernels.hip (proposal side) and csrc/detect_post.hip
+(k_perclass_nms, k_final_select) restated in plain numpy on uint64 keys, step by step as the kernels do it (NOT as a sort): key construction (make_key), the 8-pass radix select of k_select_topk with its LDS-list
 gather as a flag, the `>= cut` compaction, the counting rank of k_rank, the score recovery of k_scatter_sorted, the rank sort of
 k_perclass_nms, and the 4-pass select + class-major compaction of k_final_select.
 

@@ -264,6 +264,56 @@ def test_detect_post_num_rois_and_no_cap(dev):
     assert n == want.shape[0] and np.array_equal(got[:, 4:], want[:, 4:]) and boxes_close(got[:, :4], want[:, :4], "detect_post (num_rois, no cap) vs oracle")
 
 
+def _rows_u32(boxes):
+    """[n,4] float32 -> the rows as uint32, sorted: a multiset of boxes compared bit for bit"""
+    u = np.ascontiguousarray(boxes, dtype=f32).reshape(-1, 4).view(np.uint32)
+    return u[np.lexsort(u.T[::-1])]
+
+
+@pytest.mark.parametrize("regress", [True, False])
+def test_detect_post_stages_exactly_the_im_detect_boxes(dev, regress):
+    """One staging rule (csrc/detect_post.hip, stage_candidate): with nothing suppressed and no cut, the boxes every per-class stage --
+    hard NMS, linear and Gaussian Soft-NMS -- emits for an (image, class) are, bit for bit, the rows of ops.im_detect_boxes for that
+    class that pass r < num_rois and score > score_thresh (bbox_pred None: the un-clipped rois / im_scale); and the vote stage, given a
+    class with ONE candidate, re-derives that same box and leaves it as it is.  (B, R, C) = (2, 65, 3): one row past a wave and past a
+    Soft-NMS slot; the second image has rows past its count.  No row is excluded from the comparison."""
+    from frcnn_hip import ops
+    B, R, C, scale, im_h, im_w, thresh = 2, 65, 3, 1.6, 375, 625, 0.1
+    num = np.array([65, 40], dtype=np.int32)
+    parts = [synth.rcnn_outputs(R, C, seed=31 + b) for b in range(B)]
+    prob, bp, rois = (np.concatenate([p[k] for p in parts]) for k in range(3))
+    t_prob, t_bp, t_rois, t_num = T(prob, dev), (T(bp, dev) if regress else None), T(rois, dev), T(num, dev)
+    want, passing = {}, {}
+    for b in range(B):
+        rows = slice(b * R, (b + 1) * R)
+        if regress:
+            boxes = ops.im_detect_boxes(T(rois[rows], dev), T(bp[rows], dev), scale, im_h, im_w).cpu().numpy().reshape(R, C, 4)
+        else:
+            boxes = np.repeat((rois[rows, 1:5].astype(np.float64) / scale).astype(f32)[:, None, :], C, axis=1)
+        for j in range(1, C):
+            ok = (np.arange(R) < num[b]) & (prob[rows, j] > f32(thresh))
+            assert ok.sum() >= 10, "the comparison must not be vacuous"
+            want[b, j], passing[b, j] = boxes[:, j], ok
+
+    def run(soft, score_thresh, vote=0.0):
+        # nms_thresh 1.5 under the CPU rule `ovr >= thresh`: no IoU reaches it, so hard NMS suppresses nothing and the linear weight is 1
+        dets, cnt = ops.detect_post(t_prob, t_bp, t_rois, t_num, scale, im_h, im_w, nms_thresh=1.5, score_thresh=score_thresh,
+                                    max_per_image=0, batch=B, soft=soft, min_score=0.0, vote=vote)
+        dets, cnt = dets.cpu().numpy(), cnt.cpu().numpy()
+        return {(b, j): dets[b, :cnt[b]][dets[b, :cnt[b], 5] == j][:, :4] for b in range(B) for j in range(1, C)}
+
+    for soft in (0, 1, 2):
+        got = run(soft, thresh)
+        for key, ok in passing.items():
+            assert np.array_equal(_rows_u32(got[key]), _rows_u32(want[key][ok])), ("soft", soft, "image, class", key)
+        for (b, j), ok in passing.items():
+            s = np.where(ok, prob[b * R:(b + 1) * R, j], -np.inf)
+            top, second = np.argsort(-s, kind="stable")[:2]
+            voted = run(soft, float(s[second]), vote=1.0)[b, j]                      # `>` the second score: one candidate in (b, j)
+            assert voted.shape == (1, 4) and np.array_equal(voted.view(np.uint32), want[b, j][top:top + 1].view(np.uint32)), \
+                ("vote", "soft", soft, "image, class", (b, j))
+
+
 def test_bbox_overlaps_bit_exact(dev, golden):
     from frcnn_hip import ops
     d = synth.random_dets(600, seed=13)[:, :4].astype(np.float64)

@@ -1,4 +1,5 @@
-"""The ordering machinery of csrc/detect_kernels.hip on the CPU: oracle/select_ref.py restates make_key, the radix select, the
+"""The ordering machinery of csrc/detect_kernels.hip (proposal side) and csrc/detect_post.hip (k_perclass_nms, k_final_select) on the
+CPU: oracle/select_ref.py restates make_key, the radix select, the
 compaction, the counting rank, the score recovery and k_final_select in numpy; oracle/score_cases.py states the tied, saturated
 and non-finite score vectors.  Shown here:
   * the unmutated restatement equals oracle/frcnn_oracle.py (order_desc / proposal_layer / proposal_top_layer / test_net_post) on

@@ -1,4 +1,4 @@
-"""GPU: the ordering machinery of csrc/detect_kernels.hip -- make_key, k_select_topk, k_rank / k_scatter_sorted, the rank sort of
+"""GPU: the ordering machinery of csrc/detect_kernels.hip (proposal side) and csrc/detect_post.hip (per class, final cut) -- make_key, k_select_topk, k_rank / k_scatter_sorted, the rank sort of
 k_perclass_nms, k_final_select -- under tied, saturated and non-finite scores (oracle/score_cases.py), through every entry point
 that sorts or cuts: the proposal layers, the NMS entry points and detect_post.
 

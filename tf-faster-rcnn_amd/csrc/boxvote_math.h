@@ -1,5 +1,5 @@
 // Bounding-box voting (Gidaris & Komodakis 2015, "Object detection via a multi-region & semantic segmentation-aware CNN model";
-// Detectron's TEST.BBOX_VOTE) and the merge of an image's two horizontal-flip views, as plain host + device C++: csrc/detect_kernels.hip
+// Detectron's TEST.BBOX_VOTE) and the merge of an image's two horizontal-flip views, as plain host + device C++: csrc/detect_post.hip
 // (the kernels k_perclass_vote / k_box_vote / k_merge_flip_views and the host entries frcnn_box_vote_host / frcnn_merge_flip_views_host)
 // and the stand-alone harness csrc/box_vote_host_check.cc include this one statement.
 //

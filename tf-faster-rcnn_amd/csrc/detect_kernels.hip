@@ -1,13 +1,13 @@
-// Detection-side kernels of libfrcnn_hip.so (gfx950, wave64): anchors, box codec, (score,index)
-// rank sort, bitmask NMS with an on-device greedy reduce, proposal layers, per-class
-// post-processing, crop_and_resize, IoU matrix.
+// Proposal-side kernels of libfrcnn_hip.so (gfx950, wave64): anchors, box codec, (score,index)
+// rank sort, bitmask NMS with an on-device greedy reduce, proposal layers, crop_and_resize,
+// bbox transforms, IoU matrix.  The test-time post-processing lives in detect_post.hip; what the
+// two share is in nms_shared.h.
 //
 // These are HBM/latency-bound integer+f32 kernels; they are NOT reshaped into GEMMs.  The TU is
 // compiled with -ffp-contract=off so every f32 op keeps its own rounding, as in the reference's
 // numpy / Cython code (citations relative to /root/reference/lib).
 #include "common.h"
-#include "softnms_math.h"
-#include "boxvote_math.h"
+#include "nms_shared.h"
 
 // ------------------------------------------------------------------------------------------------
 // anchors  (layer_utils/generate_anchors.py:41-105, layer_utils/snippets.py:14-30)
@@ -65,9 +65,6 @@ extern "C" int frcnn_generate_anchors_pre(int height, int width, int feat_stride
 // image (`SortWs`, stride `img` bytes); tensors of image b start at base + b * per-image size.  The reference graph is
 // batch-1 (lib/nets/network.py:388); a batch here is B independent images whose launches are shared.
 // ------------------------------------------------------------------------------------------------
-#define NMS_RULE_CPU FRCNN_NMS_RULE_CPU    // (double)ovr >= thresh   lib/nms/cpu_nms.pyx:65
-#define NMS_RULE_GPU FRCNN_NMS_RULE_GPU    // ovr > (float)thresh     lib/nms/nms_kernel.cu:71, lib/nms/py_cpu_nms.py:35
-#define NMS_RULE_TF 2                      // tf.image.non_max_suppression (internal: frcnn_non_max_suppression / *_tf)
 
 // ------------------------------------------------------------------------------------------------
 // stage 1 of proposal_layer: fused anchor generation + bbox_transform_inv + clip_boxes + sort key
@@ -85,6 +82,7 @@ __global__ void k_decode_clip_key(const float* __restrict__ prob, const float4* 
   const int a = n % A, pix = n / A;
   const float score = prob[(size_t)pix * 2 * A + A + a];                  // fg = channels [A,2A)  (:27)
   float4 bx = decode_box(anchor_at(base, n, A, W, stride), deltas[n]);
+  // proposal_layer's clip_boxes clamps every coordinate on BOTH sides: a different reference rule from detect_post.hip's decode_clip
   bx.x = rmax(rmin(bx.x, hi_x), 0.0f);                                    // np.maximum(np.minimum(v, dim-1), 0)
   bx.y = rmax(rmin(bx.y, hi_y), 0.0f);
   bx.z = rmax(rmin(bx.z, hi_x), 0.0f);
@@ -120,34 +118,8 @@ __global__ void k_boxes_scores_key(const float4* __restrict__ in_boxes, const fl
 // scores -- a constant or saturated RPN map -- leave the last four passes (shift 24...0) to decide the cut, and more than SEL_LIST keys
 // in the cut's 16-bit bucket keep all eight passes on the global scan.  tests/test_select_gpu.py runs both on tied, saturated and
 // non-finite scores (oracle/score_cases.py).  Reads 8N bytes nine times out of L2; replaces an O(N^2) counting sort
-// over all anchors.
+// over all anchors.  (pick_bin, one radix-select step: nms_shared.h.)
 // ------------------------------------------------------------------------------------------------
-// One radix-select step over a 256-bin histogram: the bin that holds the k-th largest key and the number of keys in the bins
-// above it.  Parallel suffix sum (shuffles inside the four 64-bin waves, then the wave totals); a serial walk by one thread
-// costs ~10 us of dependent LDS round trips per pass.  Called by EVERY thread of the workgroup (barriers inside); k must not
-// exceed the histogram total.
-__device__ __forceinline__ void pick_bin(const int* hist, int k, int* wtot, int* out_bin, int* out_above) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int h = 0, x = 0;
-  if (tid < 256) {
-    h = hist[tid];
-    x = h;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_down(x, off, 64);
-      if (lane + off < 64) x += y;                       // inclusive suffix sum inside the wave
-    }
-    if (lane == 0) wtot[wave] = x;
-  }
-  __syncthreads();
-  if (tid < 256) {
-    int above = 0;
-    for (int w = wave + 1; w < 4; ++w) above += wtot[w];
-    const int excl = x - h + above;                      // keys in bins > tid
-    if (excl < k && k <= excl + h) { *out_bin = tid; *out_above = excl; }
-  }
-  __syncthreads();
-}
-
 #define SEL_LIST 4096
 __global__ __launch_bounds__(1024) void k_select_topk(const u64* __restrict__ keys_all, int N, int K,
                                                       u64* __restrict__ ckeys_all, u32* __restrict__ rank_all, size_t img) {
@@ -304,15 +276,6 @@ __global__ void k_scatter_sorted(const float4* __restrict__ boxes_all, const u64
 // needed.  Only the upper triangle (column tile >= row tile) is computed and ever read.  grid = (cb, ceil(cb/4), B).
 // ------------------------------------------------------------------------------------------------
 template <int RULE>
-__device__ __forceinline__ float rule_area(const float4 b) { return RULE == NMS_RULE_TF ? box_area_tf(b) : box_area(b); }
-template <int RULE>
-__device__ __forceinline__ bool rule_suppresses(const float4 a, float aa, const float4 b, float ab, float thr) {
-  if (RULE == NMS_RULE_TF) return iou_suppresses_tf(a, aa, b, ab, thr);
-  if (RULE == NMS_RULE_GPU) return iou_suppresses_gt(a, aa, b, ab, thr);
-  return iou_suppresses(a, aa, b, ab, thr);
-}
-
-template <int RULE>
 __global__ __launch_bounds__(256) void k_nms_mask(const float4* __restrict__ boxes_all, int K, int cb, float thr,
                                                   u64* __restrict__ mask_all, size_t img) {
   __shared__ float4 cbox[64];
@@ -347,7 +310,7 @@ __global__ __launch_bounds__(256) void k_nms_mask(const float4* __restrict__ box
 // stage 5: greedy reduce on device (the reference does this on the host after a D2H copy of the
 // whole mask, nms_kernel.cu:118-140).
 //
-// resolve_chunk: the 64 in-chunk decisions from the chunk's diagonal words, scalar bit operations.
+// resolve_chunk (nms_shared.h): the 64 in-chunk decisions from the chunk's diagonal words, scalar bit operations.
 // k_nms_reduce<WPL>: one 1024-thread workgroup per image walks the boxes in 64-box chunks.  The 64 mask rows of chunk c+1
 // and c+2 (every word >= c+1: 4 rows per wave, WPL words per lane) are loaded into registers WHILE chunk c is being decided, so no
 // decision waits for HBM/L2 latency: per chunk the cost is one diagonal resolve on wave 0 plus an LDS atomic-OR of the kept
@@ -356,22 +319,6 @@ __global__ __launch_bounds__(256) void k_nms_mask(const float4* __restrict__ box
 // ------------------------------------------------------------------------------------------------
 // Workgroup barrier that orders LDS traffic only: __syncthreads() would also drain vmcnt and with it the prefetched mask rows.
 __device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// `cur` (wave-uniform): bit b set = box b of the chunk is already removed (or past the end).  d: lane b holds the diagonal
-// mask word of box b (bits > b only).  One iteration per KEPT box (not per box): next survivor = lowest clear bit.
-__device__ __forceinline__ u64 resolve_chunk(u64 d, u64 cur) {
-  u64 kept = 0;
-  u64 avail = ~cur;
-  while (avail) {
-    const int b = __builtin_amdgcn_readfirstlane(__ffsll((long long)avail) - 1);
-    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)d, b);
-    const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(d >> 32), b);
-    kept |= (1ull << b);
-    cur |= (((u64)hi << 32) | (u64)lo);
-    avail = (b == 63) ? 0ull : (~cur & ((~0ull) << (b + 1)));
-  }
-  return kept;
-}
 
 struct ReduceOut {
   const float4* sboxes; const float* sscores; const int* sidx;     // per-image scratch (stride img)
@@ -555,39 +502,6 @@ __global__ __launch_bounds__(64) void k_nms_reduce_wide(const u64* __restrict__ 
   reduce_finish(o, b, max_keep, min(total, max_keep), 64);
 }
 
-// Greedy scan of a mask held in LDS (the per-class stage): one wave, mask rows `words` (<= 64) u64 wide; lane w owns the
-// removed-bit word w.
-template <typename Emit>
-__device__ __forceinline__ int greedy_reduce_lds(const u64* mask, int K, int words, Emit emit) {
-  const int lane = threadIdx.x & 63;
-  u64 remv = 0ull;
-  int total = 0;
-  for (int c = 0; c < words; ++c) {
-    const int i = c * 64 + lane;
-    const u64 d = (i < K) ? mask[(size_t)i * words + c] : 0ull;
-    const u64 sel = shfl_u64(remv, c);
-    const u32 cur_lo = (u32)__builtin_amdgcn_readfirstlane((u32)sel);
-    const u32 cur_hi = (u32)__builtin_amdgcn_readfirstlane((u32)(sel >> 32));
-    u64 cur = ((u64)cur_hi << 32) | (u64)cur_lo;
-    const int nvalid = min(64, K - c * 64);
-    if (nvalid < 64) cur |= (~0ull) << nvalid;
-    const u64 kept = resolve_chunk(d, cur);
-    if ((kept >> lane) & 1ull) emit(total + __popcll(kept & ((1ull << lane) - 1ull)), i);
-    total += __popcll(kept);
-    if (lane > c && lane < words) {
-      u64 acc = remv;
-      u64 kk = kept;
-      while (kk) {
-        const int bq = __ffsll((long long)kk) - 1;
-        kk &= kk - 1;
-        acc |= mask[(size_t)(c * 64 + bq) * words + lane];
-      }
-      remv = acc;
-    }
-  }
-  return total;
-}
-
 // proposal_top_layer gather (proposal_top_layer.py:46-55)
 __global__ void k_top_rois(const float4* __restrict__ sboxes, const float* __restrict__ sscores, int K,
                            float* __restrict__ rois, float* __restrict__ scores) {
@@ -611,7 +525,7 @@ __global__ void k_decode_gather(const float* __restrict__ prob, const float4* __
   n = n < 0 ? 0 : (n >= N ? N - 1 : n);
   const int a = n % A, pix = n / A;
   float4 bx = decode_box(anchor_at(base, n, A, W, stride), deltas[n]);
-  bx.x = rmax(rmin(bx.x, hi_x), 0.0f);
+  bx.x = rmax(rmin(bx.x, hi_x), 0.0f);                                    // clip_boxes, two-sided (as k_decode_clip_key)
   bx.y = rmax(rmin(bx.y, hi_y), 0.0f);
   bx.z = rmax(rmin(bx.z, hi_x), 0.0f);
   bx.w = rmax(rmin(bx.w, hi_y), 0.0f);
@@ -681,10 +595,6 @@ static int launch_reduce(const SortWs& s, int K, int B, int max_keep, const Redu
   return FRCNN_OK;
 }
 
-// threshold as the kernels compare it (f32): CPU rule `(double)ovr >= thresh` <=> ovr >= smallest f32 >= thresh;
-// GPU rule `ovr > (float)thresh` (the reference passes a float, nms/gpu_nms.pyx:30); TF rule `iou > iou_threshold` (float attr).
-static float rule_threshold(double thresh, int rule) { return rule == NMS_RULE_CPU ? thresh_to_f32(thresh) : (float)thresh; }
-static bool rule_ok(int rule) { return rule == NMS_RULE_CPU || rule == NMS_RULE_GPU; }
 #define NMS_MAX_BOXES (64 * NMS_WIDE_WORDS)
 
 extern "C" size_t frcnn_nms_workspace_bytes(int max_boxes) {
@@ -1218,711 +1128,5 @@ extern "C" int frcnn_bbox_overlaps(const double* boxes_d, int n, const double* q
   hipLaunchKernelGGL(k_bbox_overlaps, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, boxes_d, n,
                      query_d, k, out_d);
   LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// test-time post-processing (model/test.py:95-102 and :162-180), batched over B images
-// kernel A: one workgroup per (foreground class, image): score filter, rois/scale, decode, final clip, rank sort,
-//           suppression bitmask and greedy reduce -- all in LDS (the mask of 1024 x 16 words reuses the sort scratch).
-// kernel B: one workgroup per image: exact max_per_image-th score by 4-pass radix select, then an
-//           order-preserving compaction (wave ballot + popcount prefix) into the record list.
-// ------------------------------------------------------------------------------------------------
-// im_detect's box stage alone (model/test.py:95-102): rois/scale, decode for EVERY class, final clip.
-__global__ void k_im_detect_boxes(const float* __restrict__ rois, const float* __restrict__ bbox_pred, int R, int C,
-                                  double im_scale, float hi_x, float hi_y, float4* __restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= R * C) return;
-  const int r = t / C;
-  const float* ro = rois + 5 * (size_t)r;
-  const float4 box = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
-                                 (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));
-  float4 b = box;                                                          // TEST.BBOX_REG False (test.py:103-105): np.tile(boxes), no clip
-  if (bbox_pred) {
-    b = decode_box(box, ((const float4*)bbox_pred)[t]);
-    b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);
-    b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
-  }
-  out[t] = b;
-}
-
-extern "C" int frcnn_im_detect_boxes(const float* rois_d, const float* bbox_pred_d, int R, int C, double im_scale, int im_h,
-                                     int im_w, float* boxes_d, void* stream) {
-  if (R < 0 || C <= 0 || !(im_scale > 0)) return FRCNN_E_ARG;
-  if (R == 0) return FRCNN_OK;
-  if (!rois_d || !boxes_d) return FRCNN_E_ARG;          // bbox_pred_d NULL: cfg.TEST.BBOX_REG False
-  hipLaunchKernelGGL(k_im_detect_boxes, dim3(cdiv(R * C, 256)), dim3(256), 0, (hipStream_t)stream, rois_d, bbox_pred_d, R, C,
-                     im_scale, (float)(im_w - 1), (float)(im_h - 1), (float4*)boxes_d);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-#define PC_MAXR 1024
-#define PC_THREADS 1024          // the 64x64-IoU mask rows of a class are the bulk of the work: spread them over 16 waves
-
-// dynamic LDS: sboxes float4[Rp] | sscores float[Rp] | union { keys u64[Rp] + boxes float4[Rp] ; mask u64[Rp * Rp/64] }
-static size_t perclass_lds_bytes(int R) {
-  const size_t Rp = (size_t)align_up((size_t)R, 64);
-  const size_t sort_b = Rp * (sizeof(u64) + sizeof(float4)), mask_b = Rp * (Rp / 64) * sizeof(u64);
-  return Rp * (sizeof(float4) + sizeof(float)) + (sort_b > mask_b ? sort_b : mask_b);
-}
-
-template <int RULE>
-__global__ __launch_bounds__(PC_THREADS) void k_perclass_nms(const float* __restrict__ prob_all, const float* __restrict__ bbox_pred_all,
-                                                      const float* __restrict__ rois_all, const int* __restrict__ num_rois,
-                                                      int R, int C, double im_scale, float hi_x, float hi_y, float thr,
-                                                      float score_thresh, float* __restrict__ cls_dets_all,
-                                                      int* __restrict__ cls_count_all) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char pc_smem[];
-  __shared__ int nvalid_s;
-  const int Rp = (R + 63) & ~63;
-  float4* sboxes = (float4*)pc_smem;
-  float* sscores = (float*)(sboxes + Rp);
-  unsigned char* un = (unsigned char*)(sscores + Rp);
-  u64* keys = (u64*)un;
-  float4* boxes = (float4*)(keys + Rp);
-  u64* mask = (u64*)un;                                 // valid after the sort: keys / boxes are dead by then
-  const int j = blockIdx.x + 1;                         // class; 0 is background (test.py:162)
-  const int img = blockIdx.y, nfg = C - 1;
-  const float* prob = prob_all + (size_t)img * R * C;
-  const float* bbox_pred = bbox_pred_all + (size_t)img * R * 4 * C;
-  const float* rois = rois_all + (size_t)img * R * 5;
-  float* out = cls_dets_all + ((size_t)img * nfg + blockIdx.x) * (size_t)R * 5;
-  const int tid = threadIdx.x;
-  const int nr = num_rois ? min(num_rois[img], R) : R;
-  if (tid == 0) nvalid_s = 0;
-  __syncthreads();
-  for (int r = tid; r < R; r += PC_THREADS) {
-    const float s = prob[(size_t)r * C + j];
-    const bool valid = (r < nr) && (s > score_thresh);                                   // test.py:163
-    float4 b = make_float4(0, 0, 0, 0);
-    if (valid) {
-      const float* ro = rois + 5 * (size_t)r;
-      const float4 box = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
-                                     (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));  // test.py:95
-      b = box;                                                                             // TEST.BBOX_REG False: test.py:103-105
-      if (bbox_pred_all) {
-        const float4 d = *(const float4*)(bbox_pred + (size_t)r * 4 * C + 4 * j);
-        b = decode_box(box, d);                                                            // test.py:101
-        b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);                                      // test.py:67-77
-        b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
-      }
-      atomicAdd(&nvalid_s, 1);
-    }
-    boxes[r] = b;
-    keys[r] = valid ? make_key(s, (u32)r) : (u64)(0xffffffffu - (u32)r);                  // invalid rows sort last
-  }
-  __syncthreads();
-  const int nv = nvalid_s;
-  for (int r = tid; r < R; r += PC_THREADS) {
-    const u64 mine = keys[r];
-    int rk = 0;
-    for (int q = 0; q < R; ++q) rk += (keys[q] > mine) ? 1 : 0;
-    if (rk < nv) {
-      sboxes[rk] = boxes[r];
-      sscores[rk] = key_score(mine);
-    }
-  }
-  __syncthreads();                                      // keys / boxes dead from here: the mask takes their place
-  const int words = (nv + 63) / 64;
-  for (int t = tid; t < nv * words; t += PC_THREADS) {
-    const int i = t / words, w = t % words;
-    u64 bits = 0;
-    if (w >= (i >> 6)) {
-      const float4 bi = sboxes[i];
-      const float ai = box_area(bi);
-      const int nj = min(64, nv - w * 64);
-      for (int q = 0; q < nj; ++q) {
-        const int gj = w * 64 + q;
-        if (gj > i) {
-          const float4 bj = sboxes[gj];
-          if (rule_suppresses<RULE>(bi, ai, bj, box_area(bj), thr)) bits |= (1ull << q);
-        }
-      }
-    }
-    mask[(size_t)i * words + w] = bits;
-  }
-  __syncthreads();
-  if (tid < 64) {
-    const int n = (nv > 0) ? greedy_reduce_lds(mask, nv, words, [&](int pos, int i) {
-      const float4 b = sboxes[i];
-      float* o = out + 5 * (size_t)pos;
-      o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = sscores[i];
-    }) : 0;
-    if (tid == 0) cls_count_all[(size_t)img * nfg + blockIdx.x] = n;
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_final_select(const float* __restrict__ cls_dets_all, const int* __restrict__ cls_count_all,
-                                                       int nfg, int R, int max_per_image, float* __restrict__ out_dets_all,
-                                                       int* __restrict__ out_count, int max_out, long long out_stride) {
-  __shared__ int hist[256];
-  __shared__ int wave_off[16];
-  __shared__ u32 sel_prefix, sel_mask;
-  __shared__ int sel_k, total_s, running_s, pick_b, pick_a;
-  __shared__ int wtot[4];
-  const int img = blockIdx.x;
-  const float* cls_dets = cls_dets_all + (size_t)img * nfg * R * 5;
-  const int* cls_count = cls_count_all + (size_t)img * nfg;
-  float* out_dets = out_dets_all + (size_t)img * (size_t)out_stride;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int span = nfg * R;
-  if (tid == 0) { total_s = 0; running_s = 0; }
-  __syncthreads();
-  for (int t = tid; t < nfg; t += 1024) atomicAdd(&total_s, cls_count[t]);
-  __syncthreads();
-  const int total = total_s;
-  u32 cut = 0;                                              // keep everything (test.py:175: only if len > max)
-  if (max_per_image > 0 && total > max_per_image) {
-    if (tid == 0) { sel_prefix = 0; sel_mask = 0; sel_k = max_per_image; }
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) hist[tid] = 0;
-      __syncthreads();
-      const u32 pf = sel_prefix, mk = sel_mask;
-      for (int t = tid; t < span; t += 1024) {
-        const int c = t / R, p = t % R;
-        if (p < cls_count[c]) {
-          const u32 key = sortable_u32(cls_dets[(size_t)t * 5 + 4]);
-          if ((key & mk) == pf) atomicAdd(&hist[(key >> shift) & 255], 1);
-        }
-      }
-      __syncthreads();
-      pick_bin(hist, sel_k, wtot, &pick_b, &pick_a);
-      if (tid == 0) {
-        sel_k -= pick_a;
-        sel_prefix |= ((u32)pick_b << shift);
-        sel_mask |= (255u << shift);
-      }
-      __syncthreads();
-    }
-    cut = sel_prefix;                                       // key of np.sort(scores)[-max_per_image]
-  }
-  // order-preserving compaction, class-major
-  for (int base = 0; base < span; base += 1024) {
-    const int t = base + tid;
-    bool f = false;
-    if (t < span) {
-      const int c = t / R, p = t % R;
-      f = (p < cls_count[c]) && (sortable_u32(cls_dets[(size_t)t * 5 + 4]) >= cut);     // test.py:178 `>=`
-    }
-    const u64 bal = __ballot(f);
-    if (lane == 0) wave_off[wave] = __popcll(bal);
-    __syncthreads();
-    int off = running_s;
-    for (int w = 0; w < wave; ++w) off += wave_off[w];
-    if (f) {
-      const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
-      if (pos < max_out) {
-        const float* d = cls_dets + (size_t)t * 5;
-        float* o = out_dets + (size_t)pos * 6;
-        o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3]; o[4] = d[4];
-        o[5] = (float)(t / R + 1);
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int w = 0; w < 16; ++w) s += wave_off[w];
-      running_s += s;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) out_count[img] = running_s;
-  for (int p = running_s + tid; p < max_out; p += 1024) {
-    float* o = out_dets + (size_t)p * 6;
-    o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.0f;
-  }
-}
-
-extern "C" size_t frcnn_detect_post_batched_workspace_bytes(int B, int R, int C) {
-  const size_t nfg = (size_t)(C > 1 ? C - 1 : 1), b = (size_t)(B > 0 ? B : 1), r = (size_t)(R > 0 ? R : 1);
-  return align_up(b * nfg * r * 5 * sizeof(float), 256) + align_up(b * nfg * sizeof(int), 256);
-}
-extern "C" size_t frcnn_detect_post_workspace_bytes(int R, int C) { return frcnn_detect_post_batched_workspace_bytes(1, R, C); }
-
-extern "C" int frcnn_detect_post_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
-                                         const int* num_rois_d, int B, int R, int C, double im_scale, int im_h, int im_w,
-                                         double nms_thresh, int rule, float score_thresh, int max_per_image, float* out_dets_d,
-                                         int* out_count_d, int max_out, long long out_stride, void* ws, size_t ws_bytes,
-                                         void* stream) {
-  if (!cls_prob_d || !rois_d || !out_dets_d || !out_count_d || !ws) return FRCNN_E_ARG;          // bbox_pred_d NULL: TEST.BBOX_REG False
-  if (B <= 0 || R <= 0 || C < 2 || max_out <= 0 || !(im_scale > 0) || !rule_ok(rule)) return FRCNN_E_ARG;
-  if (out_stride == 0) out_stride = (long long)max_out * 6;
-  if (out_stride < (long long)max_out * 6) return FRCNN_E_ARG;
-  if (R > PC_MAXR) return FRCNN_E_UNSUPPORTED;
-  if (frcnn_detect_post_batched_workspace_bytes(B, R, C) > ws_bytes) return FRCNN_E_WS;
-  const int nfg = C - 1;
-  char* p = (char*)ws;
-  float* cls_dets = (float*)p;
-  p += align_up((size_t)B * nfg * R * 5 * sizeof(float), 256);
-  int* cls_count = (int*)p;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = perclass_lds_bytes(R);
-  const float thr = rule_threshold(nms_thresh, rule);
-  auto kern = rule == NMS_RULE_GPU ? k_perclass_nms<NMS_RULE_GPU> : k_perclass_nms<NMS_RULE_CPU>;
-  if (lds > 48 * 1024)      // beyond the default dynamic-LDS limit (R > ~512); not a stream operation, legal during capture
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(PC_THREADS), lds, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale,
-                     (float)(im_w - 1), (float)(im_h - 1), thr, score_thresh, cls_dets, cls_count);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_final_select, dim3(B), dim3(1024), 0, st, cls_dets, cls_count, nfg, R, max_per_image, out_dets_d,
-                     out_count_d, max_out, out_stride);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_detect_post(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
-                                 const int* num_rois_d, int R, int C, double im_scale, int im_h, int im_w,
-                                 double nms_thresh, float score_thresh, int max_per_image, float* out_dets_d,
-                                 int* out_count_d, int max_out, void* ws, size_t ws_bytes, void* stream) {
-  return frcnn_detect_post_batched(cls_prob_d, bbox_pred_d, rois_d, num_rois_d, 1, R, C, im_scale, im_h, im_w, nms_thresh,
-                                   FRCNN_NMS_RULE_CPU, score_thresh, max_per_image, out_dets_d, out_count_d, max_out, 0, ws, ws_bytes,
-                                   stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Soft-NMS (csrc/softnms_math.h states the rule): per-class suppression that decays a neighbour's score instead of deleting it.
-// There is no bitmask to precompute: a class is a chain of up to R dependent select-then-decay steps, so ONE wave runs it with the
-// class resident in registers -- candidate r sits in lane r % 64, slot r / 64 (PL slots a lane, PL * 64 >= R, PL <= 16): box, area and
-// current score, 6 VGPRs a slot, plus one bit of a per-lane `live` word.  A step: the lane-local best key was already found while the
-// previous step decayed; the wave maximum of its score half and then of its index half (DPP all-reduce inside each row of 16, four
-// readlanes) names the winner, whose lane is r % 64, so its box comes by readlane; lane 0 stores the row; every lane decays its live
-// slots and finds its next local best in the same pass.  No LDS and no barrier anywhere.  Sixteen waves with a barrier per step would
-// spend the step on the barrier pair; the price of one wave is that the Gaussian weight's float64 polynomial (about 40 FP64
-// operations and one FP64 division a candidate) is paid PL times in sequence.  Assumed, not measured, when this was written: about
-// 150 cycles for the two reductions and the broadcast plus about 40 cycles a slot for the linear weight (IoU with its division), i.e.
-// "a few hundred cycles" a step at R = 300.  MEASURED (profiles/soft_nms.txt, 2.4 GHz assumed): 1 400 cycles a step at 2 slots, 2 700
-// (linear) / 4 500 (Gaussian) at the 5 slots of R = 300, 7 000 / 12 500 at 16 -- ten times the estimate.  Presumably a lone wave pays the
-// whole latency of every dependent VALU operation (the IEEE division alone is a chain of ten of them a slot) with nothing else to issue
-// meanwhile.  At 300 rois that is +0.10 ms (linear) / +0.21 ms (Gaussian) on the 0.055 ms of the hard stage for 8 images -- under 2 % of
-// the 8-image step -- but 0.25 ms of the 3.2 ms a one-by-one test_net image takes (309 -> 287 images/s, ResNet-50).
-// The staging is k_perclass_nms's: the r < num_rois && s > score_thresh filter, rois / im_scale, decode_box, the clip, bbox_pred NULL.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 wave_max_u32(u32 v) {       // all 64 lanes active
-  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));   // row_half_mirror
-  v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));   // row_mirror: every lane holds its row's maximum
-  const u32 a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-  const u32 c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-  return max(max(a, b), max(c, d));
-}
-__device__ __forceinline__ float readlane_f32(float v, int lane_uniform) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_uniform));
-}
-
-// the loop of softnms_math.h on one wave; emit(pos, box, score, r) is called by every lane with uniform arguments -> the count
-template <int PL, int METHOD, typename Emit>
-__device__ __forceinline__ int soft_nms_wave(float4 (&box)[PL], float (&sc)[PL], u32 live, float thr, int rule, double sigma,
-                                             float min_score, Emit emit) {
-  const u32 lane = threadIdx.x;
-  float ar[PL];
-  u32 bhi = 0, blo = 0;                                 // the lane's best live key; 0 = none (no finite score maps to 0)
-  float4 bb = make_float4(0, 0, 0, 0);
-  float ba = 0.0f, bs = 0.0f;                           // bs: the best slot's score itself (the key does not hold a zero's sign)
-#pragma unroll
-  for (int i = 0; i < PL; ++i) {
-    ar[i] = softnms_area(box[i].x, box[i].y, box[i].z, box[i].w);
-    const u32 hi = softnms_sortable(sc[i]);
-    if (((live >> i) & 1u) && hi > bhi) {               // slots ascend in r: `>` keeps the lower r of equal scores
-      bhi = hi, blo = ~(lane + 64u * i), bb = box[i], ba = ar[i], bs = sc[i];
-    }
-  }
-  int m = 0;
-  for (;;) {
-    const u32 whi = wave_max_u32(bhi);
-    if (whi == 0) break;                                // nothing left
-    const u32 wr = ~wave_max_u32(bhi == whi ? blo : 0u);
-    const int wl = __builtin_amdgcn_readfirstlane((int)(wr & 63u));
-    const float wscore = readlane_f32(bs, wl);
-    if (wscore < min_score) break;
-    const float4 wb = make_float4(readlane_f32(bb.x, wl), readlane_f32(bb.y, wl), readlane_f32(bb.z, wl), readlane_f32(bb.w, wl));
-    const float wa = readlane_f32(ba, wl);
-    emit(m, wb, wscore, wr);
-    ++m;
-    bhi = 0, blo = 0;
-#pragma unroll
-    for (int i = 0; i < PL; ++i) {
-      const u32 r = lane + 64u * i, bit = 1u << i;
-      if (r == wr) live &= ~bit;
-      if (live & bit) {
-        const float ov = softnms_iou(wb.x, wb.y, wb.z, wb.w, wa, box[i].x, box[i].y, box[i].z, box[i].w, ar[i]);
-        const float w = METHOD == SOFTNMS_LINEAR ? softnms_weight_linear(ov, thr, rule) : softnms_weight_gaussian(ov, sigma);
-        sc[i] = sc[i] * w;
-        const u32 hi = softnms_sortable(sc[i]);
-        if (hi > bhi) bhi = hi, blo = ~r, bb = box[i], ba = ar[i], bs = sc[i];
-      }
-    }
-  }
-  return m;
-}
-
-template <int PL, int METHOD>
-__global__ __launch_bounds__(64) void k_perclass_soft_nms(const float* __restrict__ prob_all, const float* __restrict__ bbox_pred_all,
-                                                          const float* __restrict__ rois_all, const int* __restrict__ num_rois,
-                                                          int R, int C, double im_scale, float hi_x, float hi_y, float thr, int rule,
-                                                          double sigma, float min_score, float score_thresh,
-                                                          float* __restrict__ cls_dets_all, int* __restrict__ cls_count_all) {
-  const int j = blockIdx.x + 1;                         // class; 0 is background (test.py:162)
-  const int img = blockIdx.y, nfg = C - 1;
-  const float* prob = prob_all + (size_t)img * R * C;
-  const float* bbox_pred = bbox_pred_all + (size_t)img * R * 4 * C;
-  const float* rois = rois_all + (size_t)img * R * 5;
-  float* out = cls_dets_all + ((size_t)img * nfg + blockIdx.x) * (size_t)R * 5;
-  const int lane = threadIdx.x;
-  const int nr = num_rois ? min(num_rois[img], R) : R;
-  float4 box[PL];
-  float sc[PL];
-  u32 live = 0;
-#pragma unroll
-  for (int i = 0; i < PL; ++i) {
-    const int r = lane + 64 * i;
-    float4 b = make_float4(0, 0, 0, 0);
-    float s = 0.0f;
-    if (r < R) {
-      s = prob[(size_t)r * C + j];
-      if ((r < nr) && (s > score_thresh)) {                                                // test.py:163
-        const float* ro = rois + 5 * (size_t)r;
-        const float4 bx = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
-                                      (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));  // test.py:95
-        b = bx;                                                                            // TEST.BBOX_REG False: test.py:103-105
-        if (bbox_pred_all) {
-          const float4 d = *(const float4*)(bbox_pred + (size_t)r * 4 * C + 4 * j);
-          b = decode_box(bx, d);                                                           // test.py:101
-          b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);                                    // test.py:67-77
-          b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
-        }
-        live |= 1u << i;
-      }
-    }
-    box[i] = b;
-    sc[i] = s;
-  }
-  const int n = soft_nms_wave<PL, METHOD>(box, sc, live, thr, rule, sigma, min_score, [&](int pos, float4 b, float s, u32) {
-    if (lane == 0) {                                    // pos < the class's candidates <= R
-      float* o = out + 5 * (size_t)pos;
-      o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = s;
-    }
-  });
-  if (lane == 0) cls_count_all[(size_t)img * nfg + blockIdx.x] = n;
-}
-
-// one class given as dets [k,5]: the emitted rows and their input rows in order, the rest 0 / -1, and the count
-template <int PL, int METHOD>
-__global__ __launch_bounds__(64) void k_soft_nms(const float* __restrict__ dets, int k, float thr, int rule, double sigma, float min_score,
-                                                 float* __restrict__ out_dets, int* __restrict__ out_index, int* __restrict__ out_count) {
-  const int lane = threadIdx.x;
-  float4 box[PL];
-  float sc[PL];
-  u32 live = 0;
-#pragma unroll
-  for (int i = 0; i < PL; ++i) {
-    const int r = lane + 64 * i;
-    float4 b = make_float4(0, 0, 0, 0);
-    float s = 0.0f;
-    if (r < k) {
-      const float* d = dets + 5 * (size_t)r;
-      b = make_float4(d[0], d[1], d[2], d[3]);
-      s = d[4];
-      live |= 1u << i;
-    }
-    box[i] = b;
-    sc[i] = s;
-  }
-  const int n = soft_nms_wave<PL, METHOD>(box, sc, live, thr, rule, sigma, min_score, [&](int pos, float4 b, float s, u32 r) {
-    if (lane == 0) {                                    // pos < k
-      float* o = out_dets + 5 * (size_t)pos;
-      o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = s;
-      out_index[pos] = (int)r;
-    }
-  });
-  for (int p = n + lane; p < k; p += 64) {
-    float* o = out_dets + 5 * (size_t)p;
-    o[0] = o[1] = o[2] = o[3] = o[4] = 0.0f;
-    out_index[p] = -1;
-  }
-  if (lane == 0) *out_count = n;
-}
-
-// slots a lane: 2 (n <= 128), 5 (<= 320: the 300 rois of test time), 8 (<= 512), 16 (<= 1024)
-static int soft_slots(int n) { return n <= 128 ? 2 : n <= 320 ? 5 : n <= 512 ? 8 : 16; }
-#define SOFT_PICK(KERN, pl, method)                                                                                        \
-  ((method) == SOFTNMS_LINEAR ? ((pl) == 2 ? KERN<2, 1> : (pl) == 5 ? KERN<5, 1> : (pl) == 8 ? KERN<8, 1> : KERN<16, 1>)    \
-                              : ((pl) == 2 ? KERN<2, 2> : (pl) == 5 ? KERN<5, 2> : (pl) == 8 ? KERN<8, 2> : KERN<16, 2>))
-
-extern "C" size_t frcnn_detect_post_soft_batched_workspace_bytes(int B, int R, int C) {
-  return frcnn_detect_post_batched_workspace_bytes(B, R, C);
-}
-
-extern "C" int frcnn_detect_post_soft_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
-                                              const int* num_rois_d, int B, int R, int C, double im_scale, int im_h, int im_w,
-                                              double nms_thresh, int rule, float score_thresh, int max_per_image, int method,
-                                              double sigma, float min_score, float* out_dets_d, int* out_count_d, int max_out,
-                                              long long out_stride, void* ws, size_t ws_bytes, void* stream) {
-  if (!cls_prob_d || !rois_d || !out_dets_d || !out_count_d || !ws) return FRCNN_E_ARG;          // bbox_pred_d NULL: TEST.BBOX_REG False
-  if (B <= 0 || R <= 0 || C < 2 || max_out <= 0 || !(im_scale > 0) || !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
-  if (out_stride == 0) out_stride = (long long)max_out * 6;
-  if (out_stride < (long long)max_out * 6) return FRCNN_E_ARG;
-  if (R > PC_MAXR) return FRCNN_E_UNSUPPORTED;
-  if (frcnn_detect_post_batched_workspace_bytes(B, R, C) > ws_bytes) return FRCNN_E_WS;
-  const int nfg = C - 1;
-  char* p = (char*)ws;
-  float* cls_dets = (float*)p;
-  p += align_up((size_t)B * nfg * R * 5 * sizeof(float), 256);
-  int* cls_count = (int*)p;
-  hipStream_t st = (hipStream_t)stream;
-  const int pl = soft_slots(R);
-  auto kern = SOFT_PICK(k_perclass_soft_nms, pl, method);
-  hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(64), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale,
-                     (float)(im_w - 1), (float)(im_h - 1), softnms_thresh_f32(nms_thresh, rule), rule, sigma, min_score, score_thresh,
-                     cls_dets, cls_count);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_final_select, dim3(B), dim3(1024), 0, st, cls_dets, cls_count, nfg, R, max_per_image, out_dets_d,
-                     out_count_d, max_out, out_stride);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_soft_nms(const float* dets_d, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
-                              float* out_dets_d, int* out_index_d, int* out_count_d, void* stream) {
-  if (k < 0 || !dets_d || !out_dets_d || !out_index_d || !out_count_d || !softnms_args_ok(rule, method, sigma, min_score))
-    return FRCNN_E_ARG;
-  if (k > SOFTNMS_MAX) return FRCNN_E_UNSUPPORTED;
-  auto kern = SOFT_PICK(k_soft_nms, soft_slots(k), method);
-  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, (hipStream_t)stream, dets_d, k, softnms_thresh_f32(nms_thresh, rule), rule, sigma,
-                     min_score, out_dets_d, out_index_d, out_count_d);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_soft_nms_host(const float* dets, int k, double nms_thresh, int rule, int method, double sigma, float min_score,
-                                   float* out_dets, int* out_index, int* out_count) {
-  if (k < 0 || !dets || !out_dets || !out_index || !out_count || !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
-  if (k > SOFTNMS_MAX) return FRCNN_E_UNSUPPORTED;
-  float cur[SOFTNMS_MAX];
-  uint64_t key[SOFTNMS_MAX];
-  *out_count = softnms_host(dets, k, softnms_thresh_f32(nms_thresh, rule), rule, method, sigma, min_score, cur, key, out_dets, out_index);
-  return FRCNN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Bounding-box voting and the merge of two flip views (csrc/boxvote_math.h states both rules).
-// k_perclass_vote runs between the per-class stage (hard or Soft-NMS) and k_final_select: one workgroup per (foreground class, image)
-// re-stages the class's candidates into LDS BY ROW -- k_perclass_nms's filter, rois / im_scale, decode_box and clip, hence its bits; box
-// 16 B + original score 4 B a row, 20 KB at 1024 rows, plus one validity bit a row from a wave ballot -- and then thread t owns the kept
-// detections t, t + 256, ... of cls_dets: it walks the rows in ascending order, every lane of a wave reading the SAME LDS address (a
-// broadcast, no bank conflict), skips the rows that are no candidates (their bit is wave-uniform: no divergence), accumulates the voters in
-// double and overwrites its four coordinates in place.  The trip count is R for every thread.  256 threads: the hard stage keeps a few
-// dozen rows a class, Soft-NMS at min_score 0 up to R -- four waves, one a SIMD, cover 1024 kept rows in four rounds, and the double
-// sums are five additions and four products a VOTER against some thirty float32 operations and a division a CANDIDATE, so the float64
-// rate of the VALU is not what bounds it.  No global atomics, nothing allocated: legal on a capturing stream like its neighbours.
-// ------------------------------------------------------------------------------------------------
-#define VOTE_THREADS 256
-
-struct VoteLds {
-  float4 box[BOXVOTE_MAX];
-  float score[BOXVOTE_MAX];
-  u64 valid[BOXVOTE_MAX / 64];
-};
-
-// rows [0, nrows) of `c` are staged (nrows <= BOXVOTE_MAX); kept [m,5] -> out [m,5] (may be the same rows: a thread reads its row first)
-__device__ __forceinline__ void vote_rows(const VoteLds& c, int nrows, const float* kept, int m, double vote_thresh, float* out) {
-  const int words = (nrows + 63) >> 6;
-  for (int base = 0; base < m; base += VOTE_THREADS) {
-    const int d = base + (int)threadIdx.x;
-    const bool mine = d < m;
-    float a[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (mine)
-      for (int k = 0; k < 5; ++k) a[k] = kept[5 * (size_t)d + k];
-    const float aa = boxvote_area(a[0], a[1], a[2], a[3]);
-    BoxVoteAcc acc;
-    boxvote_clear(acc);
-    for (int w = 0; w < words; ++w) {
-      u64 bits = c.valid[w];
-      while (bits) {
-        const int r = w * 64 + (int)__builtin_ctzll(bits);
-        bits &= bits - 1;
-        const float4 b = c.box[r];
-        boxvote_see(acc, a[0], a[1], a[2], a[3], aa, b.x, b.y, b.z, b.w, c.score[r], vote_thresh);
-      }
-    }
-    if (mine) {
-      boxvote_finish(acc, a);
-      for (int k = 0; k < 5; ++k) out[5 * (size_t)d + k] = a[k];
-    }
-  }
-}
-
-__global__ __launch_bounds__(VOTE_THREADS) void k_perclass_vote(const float* __restrict__ prob_all, const float* __restrict__ bbox_pred_all,
-                                                                const float* __restrict__ rois_all, const int* __restrict__ num_rois,
-                                                                int R, int C, double im_scale, float hi_x, float hi_y, float score_thresh,
-                                                                double vote_thresh, float* __restrict__ cls_dets_all,
-                                                                const int* __restrict__ cls_count_all) {
-  __shared__ VoteLds c;
-  const int j = blockIdx.x + 1;                         // class; 0 is background (test.py:162)
-  const int img = blockIdx.y, nfg = C - 1;
-  const float* prob = prob_all + (size_t)img * R * C;
-  const float* bbox_pred = bbox_pred_all + (size_t)img * R * 4 * C;
-  const float* rois = rois_all + (size_t)img * R * 5;
-  float* dets = cls_dets_all + ((size_t)img * nfg + blockIdx.x) * (size_t)R * 5;
-  const int tid = threadIdx.x;
-  const int nr = num_rois ? min(num_rois[img], R) : R;
-  for (int base = 0; base < R; base += VOTE_THREADS) {  // R <= 1024 and base a multiple of 256 below it: r <= 1023
-    const int r = base + tid;
-    bool valid = false;
-    float4 b = make_float4(0, 0, 0, 0);
-    float s = 0.0f;
-    if (r < R) {
-      s = prob[(size_t)r * C + j];
-      valid = (r < nr) && (s > score_thresh);                                              // test.py:163
-      if (valid) {
-        const float* ro = rois + 5 * (size_t)r;
-        const float4 box = make_float4((float)((double)ro[1] / im_scale), (float)((double)ro[2] / im_scale),
-                                       (float)((double)ro[3] / im_scale), (float)((double)ro[4] / im_scale));  // test.py:95
-        b = box;                                                                           // TEST.BBOX_REG False: test.py:103-105
-        if (bbox_pred_all) {
-          const float4 dl = *(const float4*)(bbox_pred + (size_t)r * 4 * C + 4 * j);
-          b = decode_box(box, dl);                                                         // test.py:101
-          b.x = rmax(b.x, 0.0f); b.y = rmax(b.y, 0.0f);                                    // test.py:67-77
-          b.z = rmin(b.z, hi_x); b.w = rmin(b.w, hi_y);
-        }
-      }
-    }
-    const u64 bal = __ballot(valid);                    // the wave's 64 rows are one word: r >> 6 is uniform in the wave
-    c.box[r] = b;
-    c.score[r] = s;
-    if ((tid & 63) == 0) c.valid[r >> 6] = bal;
-  }
-  __syncthreads();
-  const int m = min(cls_count_all[(size_t)img * nfg + blockIdx.x], R);
-  vote_rows(c, R, dets, m, vote_thresh, dets);
-}
-
-// one class: kept [m,5] and cands [n,5] in global memory -> out [m,5]
-__global__ __launch_bounds__(VOTE_THREADS) void k_box_vote(const float* __restrict__ kept, int m, const float* __restrict__ cands, int n,
-                                                           double vote_thresh, float* __restrict__ out) {
-  __shared__ VoteLds c;
-  const int tid = threadIdx.x;
-  for (int base = 0; base < n; base += VOTE_THREADS) {  // n <= 1024: r <= 1023
-    const int r = base + tid;
-    const bool valid = r < n;
-    float4 b = make_float4(0, 0, 0, 0);
-    float s = 0.0f;
-    if (valid) {
-      const float* d = cands + 5 * (size_t)r;
-      b = make_float4(d[0], d[1], d[2], d[3]);
-      s = d[4];
-    }
-    const u64 bal = __ballot(valid);
-    c.box[r] = b;
-    c.score[r] = s;
-    if ((tid & 63) == 0) c.valid[r >> 6] = bal;
-  }
-  __syncthreads();
-  vote_rows(c, n, kept, m, vote_thresh, out);
-}
-
-#define MERGE_THREADS 128
-// one workgroup per output row (2R rows an image): the row's 5C + 5 values, see boxvote_math.h; the counts are read on the device
-__global__ __launch_bounds__(MERGE_THREADS) void k_merge_flip_views(const float* __restrict__ cls_prob, const float* __restrict__ bbox_pred,
-                                                                    const float* __restrict__ rois, const int* __restrict__ num_rois,
-                                                                    int R, int C, float wm1, float* __restrict__ out_prob,
-                                                                    float* __restrict__ out_pred, float* __restrict__ out_rois,
-                                                                    int* __restrict__ out_num) {
-  const int rp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int n0 = num_rois ? boxvote_clamp_count(num_rois[2 * b], R) : R, n1 = num_rois ? boxvote_clamp_count(num_rois[2 * b + 1], R) : R;
-  int view, row;
-  boxvote_merge_source(rp, n0, n1, &view, &row);
-  const size_t src = (size_t)(2 * b + (view > 0 ? 1 : 0)) * R + row, dst = (size_t)b * 2 * R + rp;
-  for (int j = tid; j < C; j += MERGE_THREADS) out_prob[dst * C + j] = boxvote_merge_prob(cls_prob + src * C, view, j);
-  if (bbox_pred)
-    for (int k = tid; k < 4 * C; k += MERGE_THREADS) out_pred[dst * 4 * C + k] = boxvote_merge_delta(bbox_pred + src * 4 * C, view, k);
-  if (tid < 5) out_rois[dst * 5 + tid] = boxvote_merge_roi(rois + src * 5, view, tid, wm1);
-  if (rp == 0 && tid == 0) out_num[b] = n0 + n1;
-}
-
-extern "C" size_t frcnn_detect_post_vote_batched_workspace_bytes(int B, int R, int C) {
-  return frcnn_detect_post_batched_workspace_bytes(B, R, C);
-}
-
-extern "C" int frcnn_detect_post_vote_batched(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d,
-                                              const int* num_rois_d, int B, int R, int C, double im_scale, int im_h, int im_w,
-                                              double nms_thresh, int rule, float score_thresh, int max_per_image, int method,
-                                              double sigma, float min_score, double vote_thresh, float* out_dets_d, int* out_count_d,
-                                              int max_out, long long out_stride, void* ws, size_t ws_bytes, void* stream) {
-  if (!cls_prob_d || !rois_d || !out_dets_d || !out_count_d || !ws) return FRCNN_E_ARG;          // bbox_pred_d NULL: TEST.BBOX_REG False
-  if (B <= 0 || R <= 0 || C < 2 || max_out <= 0 || !(im_scale > 0) || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
-  if (method != 0 && method != SOFTNMS_LINEAR && method != SOFTNMS_GAUSSIAN) return FRCNN_E_ARG;
-  if (method == 0 ? !rule_ok(rule) : !softnms_args_ok(rule, method, sigma, min_score)) return FRCNN_E_ARG;
-  if (out_stride == 0) out_stride = (long long)max_out * 6;
-  if (out_stride < (long long)max_out * 6) return FRCNN_E_ARG;
-  if (R > PC_MAXR) return FRCNN_E_UNSUPPORTED;
-  if (frcnn_detect_post_batched_workspace_bytes(B, R, C) > ws_bytes) return FRCNN_E_WS;
-  const int nfg = C - 1;
-  char* p = (char*)ws;
-  float* cls_dets = (float*)p;
-  p += align_up((size_t)B * nfg * R * 5 * sizeof(float), 256);
-  int* cls_count = (int*)p;
-  hipStream_t st = (hipStream_t)stream;
-  const float hi_x = (float)(im_w - 1), hi_y = (float)(im_h - 1);
-  if (method == 0) {
-    const size_t lds = perclass_lds_bytes(R);
-    auto kern = rule == NMS_RULE_GPU ? k_perclass_nms<NMS_RULE_GPU> : k_perclass_nms<NMS_RULE_CPU>;
-    if (lds > 48 * 1024)      // (as frcnn_detect_post_batched)
-      HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(PC_THREADS), lds, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale, hi_x,
-                       hi_y, rule_threshold(nms_thresh, rule), score_thresh, cls_dets, cls_count);
-  } else {
-    auto kern = SOFT_PICK(k_perclass_soft_nms, soft_slots(R), method);
-    hipLaunchKernelGGL(kern, dim3(nfg, B), dim3(64), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C, im_scale, hi_x, hi_y,
-                       softnms_thresh_f32(nms_thresh, rule), rule, sigma, min_score, score_thresh, cls_dets, cls_count);
-  }
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_perclass_vote, dim3(nfg, B), dim3(VOTE_THREADS), 0, st, cls_prob_d, bbox_pred_d, rois_d, num_rois_d, R, C,
-                     im_scale, hi_x, hi_y, score_thresh, vote_thresh, cls_dets, (const int*)cls_count);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_final_select, dim3(B), dim3(1024), 0, st, cls_dets, cls_count, nfg, R, max_per_image, out_dets_d,
-                     out_count_d, max_out, out_stride);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_box_vote(const float* kept_d, int m, const float* cands_d, int n, double vote_thresh, float* out_d, void* stream) {
-  if (m < 0 || n < 0 || !kept_d || !cands_d || !out_d || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
-  if (m > BOXVOTE_MAX || n > BOXVOTE_MAX) return FRCNN_E_UNSUPPORTED;
-  if (m == 0) return FRCNN_OK;
-  hipLaunchKernelGGL(k_box_vote, dim3(1), dim3(VOTE_THREADS), 0, (hipStream_t)stream, kept_d, m, cands_d, n, vote_thresh, out_d);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_box_vote_host(const float* kept, int m, const float* cands, int n, double vote_thresh, float* out) {
-  if (m < 0 || n < 0 || !kept || !cands || !out || !boxvote_thresh_ok(vote_thresh)) return FRCNN_E_ARG;
-  if (m > BOXVOTE_MAX || n > BOXVOTE_MAX) return FRCNN_E_UNSUPPORTED;
-  boxvote_host(kept, m, cands, n, vote_thresh, out);
-  return FRCNN_OK;
-}
-
-static bool merge_args_ok(const void* cls_prob, const void* rois, int B, int R, int C, float im_w_scaled, const void* out_prob,
-                          const void* bbox_pred, const void* out_pred, const void* out_rois, const void* out_num) {
-  return cls_prob && rois && out_prob && out_rois && out_num && (!bbox_pred || out_pred) && B > 0 && R > 0 && C >= 2 && im_w_scaled > 0;
-}
-
-extern "C" int frcnn_merge_flip_views(const float* cls_prob_d, const float* bbox_pred_d, const float* rois_d, const int* num_rois_d,
-                                      int B, int R, int C, float im_w_scaled, float* out_prob_d, float* out_pred_d, float* out_rois_d,
-                                      int* out_num_d, void* stream) {
-  if (!merge_args_ok(cls_prob_d, rois_d, B, R, C, im_w_scaled, out_prob_d, bbox_pred_d, out_pred_d, out_rois_d, out_num_d)) return FRCNN_E_ARG;
-  if (B > 65535) return FRCNN_E_ARG;
-  hipLaunchKernelGGL(k_merge_flip_views, dim3(2 * R, B), dim3(MERGE_THREADS), 0, (hipStream_t)stream, cls_prob_d, bbox_pred_d, rois_d,
-                     num_rois_d, R, C, im_w_scaled - 1.0f, out_prob_d, out_pred_d, out_rois_d, out_num_d);
-  LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-extern "C" int frcnn_merge_flip_views_host(const float* cls_prob, const float* bbox_pred, const float* rois, const int* num_rois, int B,
-                                           int R, int C, float im_w_scaled, float* out_prob, float* out_pred, float* out_rois,
-                                           int* out_num) {
-  if (!merge_args_ok(cls_prob, rois, B, R, C, im_w_scaled, out_prob, bbox_pred, out_pred, out_rois, out_num)) return FRCNN_E_ARG;
-  boxvote_merge_host(cls_prob, bbox_pred, rois, num_rois, B, R, C, im_w_scaled, out_prob, out_pred, out_rois, out_num);
   return FRCNN_OK;
 }

@@ -1,5 +1,5 @@
 // Soft-NMS (Bodla et al. 2017, "Improving Object Detection With One Line of Code"), the per-class rule as plain host + device C++:
-// csrc/detect_kernels.hip (the kernels k_perclass_soft_nms / k_soft_nms and the host entry frcnn_soft_nms_host) and the stand-alone
+// csrc/detect_post.hip (the kernels k_perclass_soft_nms / k_soft_nms and the host entry frcnn_soft_nms_host) and the stand-alone
 // harness csrc/soft_nms_host_check.cc include this one statement.
 //
 //   candidates   n boxes x1,y1,x2,y2 (float32), their float32 scores, each one's original row index r

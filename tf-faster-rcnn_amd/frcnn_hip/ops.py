@@ -531,19 +531,17 @@ def detect_post(cls_prob, bbox_pred, rois, num_rois, im_scale, im_h, im_w, nms_t
     out_stride = out.stride(0) if out.dim() == 3 else 0
     nb = lib().frcnn_detect_post_batched_workspace_bytes(B, R, C)
     ws = workspace(nb, dev, "detect_post")
+    # the three entries share their leading and trailing arguments; between them: nothing / the Soft-NMS triple / that and the vote threshold
+    head = (_ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale), int(im_h), int(im_w),
+            float(nms_thresh), int(rule), float(score_thresh), int(max_per_image))
+    tail = (_ptr(out), _ptr(count), int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
+    soft_args = (int(soft), float(sigma), float(min_score))
     if vote:
-        call("frcnn_detect_post_vote_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
-             int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), int(soft), float(sigma),
-             float(min_score), float(vote), _ptr(out), _ptr(count), int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
-        return out, count
-    if soft:
-        call("frcnn_detect_post_soft_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
-             int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), int(soft), float(sigma),
-             float(min_score), _ptr(out), _ptr(count), int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
-        return out, count
-    call("frcnn_detect_post_batched", _ptr(cls_prob), _ptr(bbox_pred), _ptr(rois), _ptr(num_rois), B, R, C, float(im_scale),
-         int(im_h), int(im_w), float(nms_thresh), int(rule), float(score_thresh), int(max_per_image), _ptr(out), _ptr(count),
-         int(max_out), int(out_stride), _ptr(ws), ws.numel(), _stream())
+        call("frcnn_detect_post_vote_batched", *head, *soft_args, float(vote), *tail)
+    elif soft:
+        call("frcnn_detect_post_soft_batched", *head, *soft_args, *tail)
+    else:
+        call("frcnn_detect_post_batched", *head, *tail)
     return out, count
 
 

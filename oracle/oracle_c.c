@@ -45,7 +45,9 @@ int oracle_cpu_nms(const float* dets, int k, const int64_t* order, double thresh
   return nkeep;
 }
 
-/* utils/bbox.pyx:15-55.  boxes [n,4] f64, query [k,qstride] f64 (cols 0..3 used) -> out [n,k] f64 */
+/* utils/bbox.pyx:15-55.  boxes [n,4] f64, query [k,qstride] f64 (cols 0..3 used) -> out [n,k] f64.  min / max are Cython's
+ * `min(a, b)` = (b < a) ? b : a with a = the box's coordinate: a NaN coordinate makes iw or ih NaN, `> 0` fails and the overlap is 0
+ * (pinned on NaN rows by oracle/gen_golden_targets.py); for ordered operands the operand order changes nothing. */
 void oracle_bbox_overlaps(const double* boxes, int n, const double* query, int k, int qstride, double* out) {
   for (int kk = 0; kk < k; ++kk) {
     const double* q = query + (size_t)kk * qstride;
@@ -53,9 +55,9 @@ void oracle_bbox_overlaps(const double* boxes, int n, const double* query, int k
     for (int nn = 0; nn < n; ++nn) {
       const double* b = boxes + 4 * (size_t)nn;
       double o = 0.0;
-      const double iw = (b[2] < q[2] ? b[2] : q[2]) - (b[0] > q[0] ? b[0] : q[0]) + 1;
+      const double iw = (q[2] < b[2] ? q[2] : b[2]) - (q[0] > b[0] ? q[0] : b[0]) + 1;
       if (iw > 0) {
-        const double ih = (b[3] < q[3] ? b[3] : q[3]) - (b[1] > q[1] ? b[1] : q[1]) + 1;
+        const double ih = (q[3] < b[3] ? q[3] : b[3]) - (q[1] > b[1] ? q[1] : b[1]) + 1;
         if (ih > 0) {
           const double ua = (b[2] - b[0] + 1) * (b[3] - b[1] + 1) + box_area - iw * ih;
           o = iw * ih / ua;

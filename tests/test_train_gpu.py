@@ -7,6 +7,7 @@ import torch
 
 import frcnn_oracle as ora
 import synth
+import target_ref
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -53,6 +54,9 @@ def test_anchor_target_layer_subsampling_contract(dev, golden):
         assert np.all(full[l == 1] == 1) and np.all(full[l == 0] == 0)             # subsets of the candidates
         assert np.allclose(ow[ow > 0], 1.0 / 256) and int((ow > 0).sum()) == 4 * 256
         assert int((iw > 0).sum()) == 4 * nfg
+        # ... and the subset itself: hash_key is a fixed function of (seed, index), restated in oracle/target_ref.py
+        want = target_ref.anchor_target_layer(base, 16, 38, 63, 600, 1000, gt, seed=seed)
+        assert np.array_equal(lab, want[0]) and np.array_equal(iw, want[2]) and np.array_equal(ow, want[3])
         outs.append(l)
     assert np.array_equal(outs[0], outs[1]) and not np.array_equal(outs[0], outs[2])  # deterministic per seed
     # the reference's sampled output has the same counts
@@ -73,6 +77,10 @@ def test_proposal_target_layer_contract_and_values(dev, golden):
     mx, am = ov.max(axis=1), ov.argmax(axis=1)
     assert nfg_c == int((mx >= 0.5).sum()) and nbg_c == int(((mx < 0.5) & (mx >= 0.0)).sum())
     assert nfg_s == min(64, nfg_c) and nfg_s + nbg_s == 256                              # proposal_target_layer.py:119-127
+    # ... and the drawn rows, in their order (the restated sampler of oracle/target_ref.py)
+    want = target_ref.proposal_target_layer(rois_in, sc_in.ravel(), gt, 21, seed=5)
+    assert np.array_equal(rois, want[0]) and np.array_equal(sc, want[1]) and np.array_equal(labels, want[2]) and np.array_equal(counts, want[6])
+    assert np.array_equal(iw, want[4]) and np.array_equal(ow, want[5]) and np.abs(tg - want[3]).max() <= 2e-5
     # every output row is one of the input rois, fg rows first
     idx = [int(np.where((rois_in == r).all(axis=1))[0][0]) for r in rois]
     assert np.all(mx[idx[:nfg_s]] >= 0.5) and np.all(mx[idx[nfg_s:]] < 0.5)

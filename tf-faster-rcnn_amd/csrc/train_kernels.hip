@@ -8,7 +8,8 @@
 // and the `k` smallest keys are kept: the same distribution (uniform k-subsets), deterministic for a
 // given seed, order-independent.  Everything that is NOT random (labels before sampling, argmax
 // assignments, regression targets, weights) is bit-/1e-6-comparable with the oracle, and tests check
-// exactly that plus the counts.
+// exactly that plus the counts; which subset a seed draws is fixed by hash_key and checked against the
+// numpy restatement oracle/target_ref.py (tests/test_targets_gpu.py).
 #include "common.h"
 #include "ohem_math.h"
 
@@ -287,6 +288,12 @@ __device__ __forceinline__ void pt_emit_row(int s, int src, bool is_fg, int assi
     }
   }
 }
+// The one place this kernel knowingly departs from the reference (:111-116): with BG_THRESH_HI > FG_THRESH the reference puts a RoI whose
+// maximum IoU lies in [FG_THRESH, BG_THRESH_HI) into BOTH index sets, so it can be drawn as foreground and again as background; the
+// `else if` below makes it foreground only.  No shipped configuration sets the thresholds that way.  (A RoI row with a NaN coordinate has
+// IoU NaN in ohem_iou_f64 and is neither at any BG_THRESH_LO; the reference's Cython min / max give it IoU 0, so it agrees at
+// BG_THRESH_LO > 0 and makes the row a background candidate at BG_THRESH_LO = 0.)  oracle/target_ref.py restates this kernel step by step;
+// tests/test_targets_gpu.py holds it to that restatement, the drawn rows and their order included.
 __global__ __launch_bounds__(1024) void k_proposal_target(const PtCand cand, int Nmax, const int* __restrict__ num_d, int C, int batch,
                                                           int fg_per_image, double fg_thresh, double bg_hi, double bg_lo,
                                                           u64 seed, const PtNorm nm, float* __restrict__ out_rois,

@@ -8,6 +8,7 @@ tree, out = os.path.abspath(sys.argv[1]), sys.argv[2]
 sys.path.insert(0, tree)
 import bench  # noqa: E402
 import torch  # noqa: E402
+from frcnn_hip import replay  # noqa: E402
 from frcnn_hip.runtime import Session  # noqa: E402
 from frcnn_hip.train import TrainState  # noqa: E402
 from model.config import cfg  # noqa: E402
@@ -34,7 +35,7 @@ for i in range(3):
     losses.append([float(v) for v in net.train_step(sess, blob, ts)])
     ledgers.append(sorted(ledger.items()))
 torch.cuda.synchronize()
-recs = [v["rec"] for k, v in sess.graphs.items() if isinstance(k, tuple) and k and k[0] == "train_replay" and v.get("rec") is not None]
+recs = [ent.rec for ent in sess.graphs.values() if isinstance(ent, replay.RecordedStep) and ent.rec is not None]
 assert len(recs) == 1 and net.replay_stats == dict(eager=1, recorded=1, replayed=1), net.replay_stats
 rec = recs[0]
 POINTERS = (ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer, ctypes.Array)

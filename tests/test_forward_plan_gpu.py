@@ -64,7 +64,7 @@ def test_a_plan_switch_toggled_on_a_live_session_gets_its_own_graph(dev):
             assert keys[-1] in sess.graphs and sum(1 for k in sess.graphs if k in keys) == len(keys)
             assert net._plan.winograd_fused_f2 == fused          # the build the graph was captured from read this setting
             outs.append({k: p[k].cpu().numpy().copy() for k in ("rois", "cls_prob", "bbox_pred")})
-        assert keys[0] != keys[1] and sess.graphs[keys[0]][0] is not sess.graphs[keys[1]][0]
+        assert keys[0] != keys[1] and sess.graphs[keys[0]].graph is not sess.graphs[keys[1]].graph
         for k in outs[0]:                                        # (the fused launch gives the bits of the three launches it replaces)
             assert np.array_equal(outs[0][k].view(np.int32), outs[1][k].view(np.int32)), k
         sess.close()

@@ -209,6 +209,47 @@ def test_propose_device_equals_forward_device(dev, res50, vgg, kind):
             assert all(torch.equal(again[k], before[k]) for k in before)
 
 
+def test_the_two_captured_chains_of_a_shape_name_one_scope_and_leave_together(dev):
+    """forward_device and propose_device of one shape each keep an entry in sess.graphs (replay.CapturedGraph), under their own keys and
+    naming the same shape scope: drop_scope of that key removes both, running them again captures afresh and gives the bits from before
+    the drop, and with one shape cached a second shape evicts the first one's two entries together.  (A session of its own at the toy
+    size of tests/test_streaming_shapes_gpu.py: the test above shares its sessions and shapes with the rest of this module.)"""
+    from frcnn_hip import replay
+    from model.config import cfg
+    old = (cfg.TEST.RPN_POST_NMS_TOP_N, cfg.HIP.GRAPH_CACHE_SHAPES)
+    cfg.TEST.RPN_POST_NMS_TOP_N = 48
+    sess, net = _net(dev, "res50", "recall_scope")
+
+    def both(h, w):
+        rng = np.random.RandomState(h + w)
+        image = torch.from_numpy((rng.rand(1, h, w, 3) * 255 - 110).astype(np.float32))
+        im_info = np.array([h, w, 1.0], dtype=np.float32)
+        img = net._stage_image(sess, image, im_info)
+        p = net.forward_device(sess, img, im_info)
+        torch.cuda.synchronize()
+        out = [p[k].clone() for k in sorted(p)] + [net._num_rois.clone()]
+        out += [t.clone() for t in net.propose_device(sess, img, im_info)]
+        torch.cuda.synchronize()
+        return net.graph_key(img.shape, im_info), out
+    try:
+        key, first = both(112, 144)
+        fwd, prop = sess.graphs[key], sess.graphs[("propose",) + key]
+        assert type(fwd) is type(prop) is replay.CapturedGraph and fwd.scope == prop.scope == key and fwd.graph is not prop.graph
+        assert set(sess.graphs) == {key, ("propose",) + key} and list(sess.scopes) == [key] and int(first[-1].min()) > 0
+        assert sess.drop_scope(key) and sess.graphs == {} and key not in sess.scopes
+        key2, again = both(112, 144)
+        assert key2 == key and set(sess.graphs) == {key, ("propose",) + key}
+        assert sess.graphs[key].graph is not fwd.graph and sess.graphs[("propose",) + key].graph is not prop.graph      # captured afresh
+        assert len(again) == len(first) and all(torch.equal(a, b) for a, b in zip(again, first))
+        cfg.HIP.GRAPH_CACHE_SHAPES = 1
+        other, _ = both(120, 160)
+        assert other != key and set(sess.graphs) == {other, ("propose",) + other} and list(sess.scopes) == [other]
+        assert sess.graphs[other].scope == sess.graphs[("propose",) + other].scope == other
+    finally:
+        cfg.TEST.RPN_POST_NMS_TOP_N, cfg.HIP.GRAPH_CACHE_SHAPES = old
+        sess.close()
+
+
 # ---- tools/rpn_recall.py on a toy devkit ------------------------------------------------------------------------------------------------
 def test_rpn_recall_tool_batches_and_decoders_agree_and_evaluate_recall_reproduces_it(dev, res50, tmp_path, monkeypatch):
     import rpn_recall

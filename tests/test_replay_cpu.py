@@ -302,7 +302,7 @@ def test_train_step_goes_eager_then_recorded_then_replayed(monkeypatch):
         assert net.replay_stats == dict(eager=1, recorded=1, replayed=2) and net._sample_seed == 8 and sess.prepared.epoch == 2
         # every step ran inside its image shape's buffer scope (Session.shape_scope), LRU group = the network tag
         assert sess.scope_log == [(("train_shape", "t", (1, 4, 6, 4)), ("train", "t"), int(cfg.HIP.TRAIN_CACHE_SHAPES))] * 4
-        assert all(e.get("scope") == ("train_shape", "t", (1, 4, 6, 4)) for k, e in sess.graphs.items() if k[0] == "train_replay")
+        assert all(e.scope == ("train_shape", "t", (1, 4, 6, 4)) for k, e in sess.graphs.items() if k[0] == "train_replay")
         net.train_step_async(sess, dict(shape=(1, 4, 8, 4), G=1), op)                 # another image shape: eager again
         assert net.replay_stats == dict(eager=2, recorded=1, replayed=2)
         sess.prepared.version += 1                                                    # filters changed behind the solver's back: not steady, no recording
@@ -443,3 +443,270 @@ def test_stream_picker_times_real_steps_and_keeps_the_fastest_binding(monkeypatc
         assert net.replay_stats["replayed"] == 3 * 3 + 2 + 1
     finally:
         cfg.HIP.TRAIN_REPLAY, cfg.HIP.TRAIN_PICK_STREAMS = old
+
+
+# ---- replay.StepReplayer and the entries of sess.graphs, driven directly: a fake session, fake streams, a fake body ------------------------
+class _Hip(object):
+    TRAIN_PICK_STREAMS, PREP_STREAM = 0, True
+
+
+class _PickingSess(_Sess):
+    """a _Sess that notes who assigns sess.picking: (value, function that assigned it)"""
+
+    def __init__(self):
+        self.__dict__["picking_set_by"] = []
+        _Sess.__init__(self)
+
+    def __setattr__(self, name, value):
+        if name == "picking":
+            self.picking_set_by.append((value, sys._getframe(1).f_code.co_name))
+        object.__setattr__(self, name, value)
+
+
+def _drive(log, sess=None, hip=None):
+    """-> step(shape name, G): one StepReplayer.step of a three-launch body on fake streams; nothing of Network, nothing of torch.cuda"""
+    main, side = _Stream("main", 0x1000, log), _Stream("side", 0x2000, log)
+    conv = FakeFn("frcnn_conv", [P, I, P], log)
+    rp, sess, hip = replay.StepReplayer(), (_Sess() if sess is None else sess), (_Hip() if hip is None else hip)
+    pool = []
+
+    def new_stream(device):
+        pool.append(_Stream("pool%d" % len(pool), 0x9000 + 16 * len(pool), log))
+        return pool[-1]
+    rp.new_stream = new_stream
+    state = dict(seed=0, restored=[])
+
+    def step(shape, G, cap=16):
+        def body(out):
+            if frcnn_hip.recorder is not None:
+                frcnn_hip.recorder.slot(side)
+            for args in ((P(0xA0), G, P(0x1000)), (P(0xC0), 9, P(0x2000))):
+                conv(*[t(a) if not isinstance(a, ctypes._SimpleCData) else a for t, a in zip(conv.argtypes, args)])
+                if frcnn_hip.recorder is not None:
+                    frcnn_hip.recorder.add_call(conv, "frcnn_conv", args)
+                    if args[0].value == 0xA0:
+                        frcnn_hip.recorder.patch_last(1, var="gt")
+            state["seed"] += 2
+
+        def restore(views, acts):
+            state["restored"].append((views, acts))
+            state["seed"] += 2
+        return rp.step(sess, main, "t/train", ("train_replay", shape), ("train_shape", shape), body=body, ready=lambda: True,
+                       snapshot=lambda: ({"views of": shape}, ["acts of", shape]), restore=restore,
+                       now=dict(seed=state["seed"], gt=G), hip=hip, cap=cap)
+    return rp, sess, hip, state, step
+
+
+def test_step_replayer_runs_on_plain_fakes():
+    log = []
+    rp, sess, hip, state, step = _drive(log)
+    for G in (3, 5, 2):
+        del log[:]
+        out = step("a", G)
+        assert log == [("frcnn_conv", 0xA0, G, 0x1000), ("frcnn_conv", 0xC0, 9, 0x2000)] and tuple(out.shape) == (5,)
+    assert rp.stats == dict(eager=1, recorded=1, replayed=1) and state["seed"] == 6
+    assert state["restored"] == [({"views of": "a"}, ["acts of", "a"])]               # the replayed step handed the recorded step's views back
+    ent = sess.graphs[("train_replay", "a")]
+    assert type(ent) is replay.RecordedStep and ent.scope == ("train_shape", "a") and (ent.seen, ent.used, ent.picker) == (2, 3, None)
+    assert ent.gen == sess.derived_generation() and ent.rec.vars == dict(seed=2, gt=5)
+    step("b", 1, cap=1)                                                               # the cap is the caller's: a's entry goes
+    assert list(sess.graphs) == [("train_replay", "b")] and frcnn_hip.recorder is None and ops.arena is None
+
+
+def test_release_is_the_only_place_that_clears_picking():
+    """sess.picking is set where a search starts (StepReplayer._replay) and cleared in RecordedStep.release and nowhere else, on every
+    way a search can end: it finishes (published), its recording is forgotten (derived set moved), its entry is evicted by the
+    replayer's cap, its shape scope is dropped."""
+    log = []
+    sess = _PickingSess()
+    rp, sess, hip, state, step = _drive(log, sess)
+    hip.TRAIN_PICK_STREAMS = 1
+    for _ in range(3):
+        step("a", 3)
+    assert sess.picking and sess.graphs[("train_replay", "a")].picker is not None
+    for _ in range(2 * 3 - 1):                                                        # the baseline window and the one candidate's
+        step("a", 3)
+    assert not sess.picking and [int(s.cuda_stream) for s in sess.picked_streams] in ([0x2000], [0x9000]) and len(sess.pick_log) == 2
+    assert sess.graphs[("train_replay", "a")].picker is None                          # (a finished search leaves the entry)
+    sess.picked_streams = None                                                        # a second search, ended by a moved derived set ...
+    step("a", 3)
+    assert sess.picking
+    sess.derived_gen += 1
+    step("a", 3)                                                                      # (recorded afresh)
+    assert not sess.picking and sess.picked_streams is None
+    step("a", 3)                                                                      # ... a third, ended by the cap ...
+    assert sess.picking
+    step("b", 3, cap=1)
+    assert not sess.picking and list(sess.graphs) == [("train_replay", "b")]
+    step("b", 3)
+    step("b", 3)                                                                      # ... a fourth, ended by hand
+    assert sess.picking
+    replay.release_entries(sess)
+    assert not sess.picking and sess.graphs == {} and sess.picked_streams is None
+    cleared = [who for value, who in sess.picking_set_by[1:] if value is False]       # ([0]: the session's own initial value)
+    assert cleared == ["release"] * 4
+    assert [who for value, who in sess.picking_set_by[1:] if value is True] == ["_replay"] * 4
+    replay.CapturedGraph("k", None, None, 0, 0, None).release(sess)                   # a captured graph has no search to end
+    assert len(sess.picking_set_by) == 1 + 8
+
+
+def test_restoring_or_closing_a_session_ends_a_running_search(monkeypatch):
+    """Before: VariableStore._drop_derived (every load / restore / init of the variables) and Session.close emptied sess.graphs with
+    dict.clear(): a stream search that was running on one of the dropped recordings was never ended, sess.picking stayed True for the
+    life of the session and no later recording could start a search (the trap ADVICE r5 describes, by another door).
+    After: both release every entry first (replay.release_entries), so picking falls with the recording and the next recording of the
+    session searches again."""
+    from frcnn_hip.runtime import Session
+
+    class Picker(object):
+        done = False
+    for drop in (lambda s: s.load_variables({}), lambda s: s.init_variables({}), Session.close):
+        sess = Session.__new__(Session)
+        sess._init_host(torch.device("cpu"), 3)
+        ent = sess.graphs[("train_replay", 1)] = replay.RecordedStep("A")
+        ent.rec, ent.picker, sess.picking = "r1", Picker(), True
+        sess.graphs["A"] = replay.CapturedGraph("A", "graph", None, 0, 0, None)
+        gen = sess.derived_generation()
+        drop(sess)
+        assert sess.graphs == {} and sess.picking is False and sess.picked_streams is None and ent.picker is None
+        assert drop is Session.close or sess.derived_generation() != gen
+
+
+def test_launch_captured_warms_up_captures_once_and_follows_the_image(monkeypatch):
+    """replay.launch_captured, the one capture-or-replay path of forward_device and propose_device: first sight of a key = wait for the
+    caller's stream, warm-up build, synchronise, capture, synchronise, entry stored with what snapshot() returned; every call = restore,
+    copy the image to where the graph reads it if the caller staged it elsewhere, launch."""
+    import contextlib
+    log = []
+    cur, own = _Stream("cur", 0x1000, log), _Stream("sess", 0x3000, log)
+
+    class Graph(object):
+        def capture(self, fn):
+            log.append("capture")
+            fn()
+            return self
+
+        def launch(self):
+            log.append("launch")
+
+    class Image(object):
+        def __init__(self, ptr):
+            self.ptr = ptr
+
+        def data_ptr(self):
+            return self.ptr
+
+        def copy_(self, src, non_blocking=False):
+            log.append(("copy", self.ptr, src.ptr, non_blocking))
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: cur)
+    monkeypatch.setattr(torch.cuda, "stream", lambda st: (log.append(("on", st.name)), contextlib.nullcontext())[1])
+    monkeypatch.setattr(ops, "Graph", Graph)
+    sess = _Sess()
+    sess.stream, sess.flops_last_forward = own, 123
+
+    def build():
+        sess.flops_last_forward += 7
+        log.append("build")
+        return "out"
+    args = dict(build=build, snapshot=lambda out: (log.append(("snapshot", out)), (48, ("state", out)))[1], restore=lambda e: log.append(("restore", e.per)))
+    a, b = Image(0xA000), Image(0xB000)
+    ent = replay.launch_captured(sess, ("propose", "k"), "k", image=a, **args)
+    assert log == [("on", "sess"), ("wait_stream", "sess", "cur"), "build", ("sync", "sess"), "capture", "build", ("sync", "sess"),
+                   ("snapshot", "out"), ("restore", 48), "launch"]
+    assert type(ent) is replay.CapturedGraph and sess.graphs == {("propose", "k"): ent}
+    assert (ent.scope, ent.image, ent.flops, ent.per, ent.state) == ("k", a, 7, 48, ("state", "out"))      # flops: of the warm-up alone
+    del log[:]
+    assert replay.launch_captured(sess, ("propose", "k"), "k", image=b, **args) is ent                       # staged elsewhere: copied first
+    assert log == [("restore", 48), ("copy", 0xA000, 0xB000, True), "launch"]
+    del log[:]
+    assert replay.launch_captured(sess, ("propose", "k"), "k", image=a, **args) is ent and log == [("restore", 48), "launch"]
+
+
+# ---- the whole state machine on one scripted scenario, against the trace recorded from the commit before it moved into replay.py ----------
+def replay_trace():
+    """One net, one session, one run through everything the recorded-step state machine decides (fixtures/gen_replay_trace.py writes
+    what this returns to tests/golden/replay_trace.json).  Per step: the launch log (entry name, argument values, stream handle last;
+    stream synchronisations and waits), replay_stats, the keys of sess.graphs (reduced to what is stable between processes: kind, tag,
+    image shape, index of the solver handle), sess.picking, sess.prepared.forgot, whether picked_streams is set, and the candidate names
+    of pick_log.  The stream search times its windows on a counted clock (a launch on the helper slot costs what `cost` says for its
+    stream), so the binding it picks is the same in every run; the timing values themselves are not part of the trace."""
+    import json
+    mp, log, steps, clock = pytest.MonkeyPatch(), [], [], [0.0]
+    net, main, side, made = _stub_net(mp, log)
+    from model.config import cfg
+    sess, ops_ = _Sess(), [_TrainOp(), _TrainOp()]
+    cost = {0x2000: 4.0, 0x9000: 1.0, 0x9010: 6.0}
+    real = FakeFn.__call__
+
+    def counted(self, *args):
+        if args[0].value == 0xC0:
+            clock[0] += cost[args[-1].value]
+        return real(self, *args)
+    mp.setattr(FakeFn, "__call__", counted)
+    mp.setattr(replay.time, "perf_counter", lambda: clock[0])
+    mp.setattr(cfg.HIP, "TRAIN_REPLAY", True)
+    mp.setattr(cfg.HIP, "TRAIN_PICK_STREAMS", 0)
+    mp.setattr(type(net), "REPLAY_CAP", 2)
+    A, B, C = ((1, 4, w, 4) for w in (6, 8, 10))
+
+    def key_of(k):
+        return [k[0], k[1], list(k[2]), [id(o) for o in ops_].index(k[6])] if k[0] == "train_replay" else list(k)
+
+    def step(what, shape, G, op=0):
+        del log[:]
+        net.train_step_async(sess, dict(shape=shape, G=G), ops_[op])
+        steps.append(dict(what=what, log=[list(e) for e in log], stats=dict(net.replay_stats), keys=sorted(key_of(k) for k in sess.graphs),
+                          picking=sess.picking, forgot=list(sess.prepared.forgot), picked=sess.picked_streams is not None,
+                          pick_log=[w for w, _ in getattr(sess, "pick_log", [])], seed=net._sample_seed))
+    try:
+        for G in (3, 5, 2, 9):                                  # one shape: eager, recorded, replayed twice; G and the seed move
+            step("A", A, G)
+        step("B eager", B, 1)
+        step("B recorded", B, 4)
+        step("C eager: A is the least recently used of 2", C, 2)
+        step("C recorded", C, 2)
+        step("C replayed", C, 6)
+        sess.derived_gen += 1
+        step("C after derived_gen moved: recorded afresh", C, 3)
+        step("C replayed", C, 3)
+        sess.prepared.gen += 1
+        sess.prepared.version += 1
+        step("C after prepared.gen moved, version ahead: eager", C, 3)
+        sess.prepared.ready_version = sess.prepared.version
+        step("C recorded", C, 7)
+        step("C replayed", C, 1)
+        body = type(net)._train_step_body
+
+        def growing(self, sess_, train_op, out):
+            sess_.derived_gen += 1
+            return body(self, sess_, train_op, out)
+        mp.setattr(type(net), "_train_step_body", growing)
+        sess.derived_gen += 1
+        step("C stale, and the set grows while the step is recorded: eager", C, 3)
+        mp.setattr(type(net), "_train_step_body", body)
+        step("C with a second solver handle: its own entry, B's goes", C, 3, op=1)
+        cfg.HIP.TRAIN_PICK_STREAMS = 2
+        step("C eager: cfg.HIP is part of the key", C, 3)
+        step("C recorded", C, 2)
+        for i in range(3 * 3 + 2):                              # baseline window + one per (slot 1, pool stream), then two steps on the result
+            step("C replayed, search step %d" % i, C, 3 + i)
+        step("B eager", B, 5)
+        step("B recorded", B, 5)
+        step("B replayed on the picked streams", B, 8)
+        cfg.HIP.TRAIN_REPLAY = False
+        step("C with TRAIN_REPLAY off", C, 3)
+    finally:
+        mp.undo()
+    return json.loads(json.dumps(steps))
+
+
+def test_the_scripted_scenario_gives_the_recorded_trace():
+    """tests/golden/replay_trace.json was written by fixtures/gen_replay_trace.py from the commit before the state machine moved out of
+    Network: every launch, stream, counter, key, eviction and search decision of the scenario is still the same."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "replay_trace.json")) as f:
+        want = json.load(f)
+    got = replay_trace()
+    assert [s["what"] for s in got] == [s["what"] for s in want]
+    for g, w in zip(got, want):
+        assert g == w, g["what"]

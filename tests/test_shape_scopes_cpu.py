@@ -53,9 +53,12 @@ def test_lru_eviction_drops_buffers_graphs_and_recordings_together(sess):
     for i, k in enumerate(["A", "B", "C"]):
         with sess.shape_scope(k, group="t", cap=3):
             sess.buf("act", (16 * (i + 1),))
-        sess.graphs[k] = ("graph", k)
-    sess.graphs[("train_replay", 1)] = dict(rec="r1", scope="A", picker=Picker())
-    sess.graphs[("train_replay", 2)] = dict(rec="r2", scope="B")
+        sess.graphs[k] = replay.CapturedGraph(k, "graph", None, 0, 0, None)          # forward_device's entry: its scope is its own key
+        sess.graphs[("propose", k)] = replay.CapturedGraph(k, "graph", None, 0, 0, None)    # propose_device's names the same scope
+    for n, k in ((1, "A"), (2, "B")):
+        sess.graphs[("train_replay", n)] = replay.RecordedStep(k)
+        sess.graphs[("train_replay", n)].rec = "r%d" % n
+    sess.graphs[("train_replay", 1)].picker = Picker()
     with sess.shape_scope("other", group="u", cap=1):                                # another group: counts separately
         sess.buf("act", (4,))
     sess.picking = True
@@ -66,6 +69,7 @@ def test_lru_eviction_drops_buffers_graphs_and_recordings_together(sess):
         sess.buf("act", (4,))
     assert len(sess.synced) == 1                                                     # the device was idle before anything was freed
     assert list(sess.scopes) == ["C", "other", "A", "D"] and "B" not in sess.graphs and ("train_replay", 2) not in sess.graphs
+    assert ("propose", "B") not in sess.graphs and {"A", ("propose", "A"), "C", ("propose", "C")} <= set(sess.graphs)
     assert sess.picking and ("train_replay", 1) in sess.graphs                       # A's recording and its running stream search live on
     with sess.shape_scope("E", group="t", cap=2):                                    # a smaller cap drops as many as needed: C and A
         pass

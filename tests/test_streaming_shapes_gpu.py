@@ -262,7 +262,7 @@ def test_training_over_changing_image_shapes_stays_bounded_and_reproducible(dev)
                 live = [s for s in sess.scopes if isinstance(s, tuple) and s and s[0] == "train_shape"]
                 recs = [key for key in sess.graphs if isinstance(key, tuple) and key and key[0] == "train_replay"]
                 most = max(most, len(live))
-                assert all(sess.graphs[key].get("scope") in sess.scopes for key in recs)       # no recording outlives its buffers
+                assert all(sess.graphs[key].scope in sess.scopes for key in recs)       # no recording outlives its buffers
             torch.cuda.synchronize()
             return losses, most, dict(net.replay_stats)
         finally:

@@ -16,11 +16,17 @@ milliseconds per step, and `StreamPicker` chooses the assi
 The few arguments that do change from step to step (the sampling seeds of the target layers, dropout seeds) are marked when they are
 recorded (`patch_last`) and rewritten at replay from the step's seed counter.
 
+The cache around it lives here too: `Session.graphs` holds one entry type (`Entry`: `CapturedGraph` for the TEST-mode hipGraphs, made and
+launched by `launch_captured`; `RecordedStep` for the training steps of one key), and `StepReplayer` decides which step of a key runs
+eagerly, which is recorded and which are replayed.
 """
 import ctypes
 import time
 
 import torch
+
+import frcnn_hip as _binding
+from . import ops
 
 
 class Arena(object):
@@ -216,6 +222,186 @@ class StreamPicker(object):
         b[0] = main
         self.rec.bind(b)
         self.done = True
+
+
+# ---- what Session.graphs holds -----------------------------------------------------------------------------------------------------------
+# One entry per key: a captured TEST-mode chain (Network.forward_device under the shape's scope key, Network.propose_device under
+# ("propose",) + that key) or the recorded training steps of one ("train_replay", ...) key.  Every entry names the shape scope whose
+# buffers it addresses, and is dropped with it (Session.drop_scope); every path that drops entries goes through release_entries().
+class Entry(object):
+    __slots__ = ("scope",)
+
+    def release(self, sess):
+        """The entry is about to be forgotten, or its recording is: a stream search that runs on it ends here.  This is the one place
+        that ends a search and clears sess.picking."""
+
+
+class CapturedGraph(Entry):
+    """A hipGraph of one image shape: the graph, the image buffer it reads, the forward pass's flop count, the rois per image and
+    whatever else of the network the build left behind and a replay has to put back (`state`: the caller's own)."""
+    __slots__ = ("graph", "image", "flops", "per", "state")
+
+    def __init__(self, scope, graph, image, flops, per, state):
+        self.scope, self.graph, self.image, self.flops, self.per, self.state = scope, graph, image, flops, per, state
+
+
+class RecordedStep(Entry):
+    """The training steps of one key: how many ran eagerly (`seen`), the LRU stamp (`used`), and once a steady step was recorded its
+    Recording, the derived-set generation it covers, the network's result views of that step and -- while the session's stream search
+    runs on this recording -- the StreamPicker."""
+    __slots__ = ("seen", "used", "rec", "gen", "views", "acts", "picker")
+
+    def __init__(self, scope):
+        self.scope, self.seen, self.used = scope, 0, 0
+        self.rec = self.gen = self.views = self.acts = self.picker = None
+
+    def release(self, sess):
+        """A finished search is published to the session (every recording with as many slots binds to its streams); one that was still
+        running is abandoned -- sess.picking must not stay set, or no other recording could ever start a search."""
+        pk, self.picker = self.picker, None
+        if pk is not None:
+            if pk.done:
+                sess.picked_streams, sess.pick_log = list(pk.best[1:]), list(pk.log)
+            sess.picking = False
+
+    def forget(self, sess):
+        """Drops the recording (kept: the `seen` count, so the next steady step records again)."""
+        self.release(sess)
+        self.rec = self.gen = self.views = self.acts = None
+
+
+def release_entries(sess, keys=None):
+    """Releases and deletes the entries of sess.graphs under `keys` (default: all of them)."""
+    for k in list(sess.graphs) if keys is None else keys:
+        sess.graphs.pop(k).release(sess)
+
+
+def launch_captured(sess, key, scope, build, image, snapshot, restore):
+    """A TEST-mode chain as one hipGraph per key.  First sight of the key: build() once on sess.stream as warm-up (allocates buffers,
+    packs weights), then captured; snapshot(what the warm-up returned) -> (rois per image, state) is kept with the graph.  Always:
+    restore(entry) puts the network's view of the results back, the image is copied to where the graph reads it when the caller staged
+    it somewhere else (its own buffer, the session-wide staging buffer vs. the shape scope's: 4 B per pixel and channel, device to
+    device, on the stream the graph is launched on), and the graph is launched on the current stream.  -> the entry"""
+    ent = sess.graphs.get(key)
+    if ent is None:
+        cur = torch.cuda.current_stream(sess.device)
+        with torch.cuda.stream(sess.stream):
+            sess.stream.wait_stream(cur)
+            sess.flops_last_forward = 0
+            out = build()
+            sess.stream.synchronize()
+            flops = sess.flops_last_forward
+            g = ops.Graph().capture(build)
+            sess.stream.synchronize()
+        per, state = snapshot(out)
+        ent = sess.graphs[key] = CapturedGraph(scope, g, image, flops, per, state)
+    restore(ent)
+    if ent.image.data_ptr() != image.data_ptr():
+        ent.image.copy_(image, non_blocking=True)
+    ent.graph.launch()
+    return ent
+
+
+class StepReplayer(object):
+    """Which training steps run eagerly, which one is recorded and which are replayed (Network.train_step_async under
+    cfg.HIP.TRAIN_REPLAY), for one network: the first step of a key is eager, the next STEADY one is recorded while it runs (solver
+    built, prepared filters current, nothing derived during the step), every later one replays the recording -- until the session's
+    derived-filter set moves on (Session.derived_generation), which costs one eager-or-recorded step.  At most `cap` keys per session
+    keep an entry, least recently used first out.  The network hands over the key, the shape scope the step's buffers live in, the step
+    itself (`body(out)`: enqueues it eagerly, the five losses into `out`) and a pair for its host-side results: snapshot() -> (views,
+    acts) after a recorded step, restore(views, acts) after a replayed one (which also owes the network the step's seed advance).
+    Nothing here needs a GPU beyond what the streams, the session and the body it is given need."""
+
+    def __init__(self):
+        self.clock, self.arena = 0, None                        # LRU clock of the entries; the static results of the ops that allocate
+        self.stats = dict(eager=0, recorded=0, replayed=0)
+
+    new_stream = staticmethod(lambda device: torch.cuda.Stream(device=device))      # (the search's pool)
+
+    def step(self, sess, main, name, key, scope, body, ready, snapshot, restore, now, hip, cap):
+        """One step on `main`, torch's current stream.  name: prefix of the step's static buffers (losses, arena); ready(): the solver
+        handle is built (asked only when a recording could start); now: the step's variables {"seed", "gt"} (Recording.replay); hip:
+        cfg.HIP; cap: entries kept.  -> the five losses, a fresh device tensor"""
+        ent = sess.graphs.get(key)
+        if ent is None:
+            ent = self._admit(sess, key, scope, cap)
+        self.clock += 1
+        ent.used = self.clock
+        out = sess.buf(name + "/losses", (5,))
+        rec = ent.rec
+        if rec is not None and ent.gen == sess.derived_generation():
+            self._replay(sess, main, ent, rec, now, restore, hip)
+            return out.clone()
+        if rec is not None:
+            # the set of derived filter images changed after the recording (a TEST-mode network's first run on this session, another
+            # shape's plan key): its refresh launches no longer cover the set -> this step runs eagerly (weights_changed + refresh see
+            # everything) and the shape is recorded again at its next steady step
+            ent.forget(sess)
+        arena = self.arena
+        if arena is None or arena.sess is not sess:
+            arena = self.arena = Arena(sess, name)
+        arena.reset()
+        prep = sess.prepared
+        steady = (ent.seen >= 1 and ready() and _binding.recorder is None
+                  and (not hip.PREP_STREAM or (prep.ready_version == prep.version and len(prep.plan) > 0 and len(prep.ready) == len(prep.plan))))
+        gen_before = sess.derived_generation()
+        ops.arena = arena
+        try:
+            if steady:
+                prep.forget_waits(main)                       # the recorded step carries every tier's wait at its first use
+                rec = Recording(main)
+                rec.vars = dict(now)
+                _binding.recorder = rec
+            body(out)
+        finally:
+            ops.arena = None
+            _binding.recorder = None
+        ent.seen += 1
+        if steady and sess.derived_generation() == gen_before:     # (a filter image derived inline during the step = not the steady state yet)
+            ent.rec, ent.gen = rec, gen_before
+            ent.views, ent.acts = snapshot()
+            self.stats["recorded"] += 1
+        else:
+            self.stats["eager"] += 1
+        return out.clone()
+
+    def _admit(self, sess, key, scope, cap):
+        live = [k for k, e in sess.graphs.items() if type(e) is RecordedStep]
+        if len(live) >= cap:
+            release_entries(sess, [min(live, key=lambda k: sess.graphs[k].used)])
+        ent = sess.graphs[key] = RecordedStep(scope)
+        return ent
+
+    def _replay(self, sess, main, ent, rec, now, restore, hip):
+        # which physical stream every helper slot runs on: inherited from the recording, or (cfg.HIP.TRAIN_PICK_STREAMS = pool size)
+        # searched once per session by timing real steps (StreamPicker) and then shared by every recording with the same slots
+        picked = sess.picked_streams
+        if ent.picker is None and picked is None and not sess.picking and int(hip.TRAIN_PICK_STREAMS) > 0:
+            ent.picker = StreamPicker(rec, main, [self.new_stream(sess.device) for _ in range(int(hip.TRAIN_PICK_STREAMS))])
+            sess.picking = True
+        pk = ent.picker
+        if pk is not None:
+            pk.before_step(main)                              # (binds the recording to the candidate it times next)
+            if pk.done:                                       # nothing to try
+                ent.release(sess)
+                pk = None
+        if pk is None:
+            helpers = picked if (picked is not None and len(picked) == len(rec.streams) - 1) else list(rec.streams[1:])
+            if rec.bound is None or [int(x.cuda_stream) for x in rec.bound] != [int(x.cuda_stream) for x in [main] + helpers]:
+                rec.bind([main] + helpers)
+        prep = sess.prepared
+        for h, st in list(prep.readers.items()):              # a TEST-mode network on another stream read the filter images since the
+            if h != int(main.cuda_stream):                    # last refresh: the list's refresh waits for `main` only, so main waits for it
+                main.wait_stream(st)
+        prep.readers = {}
+        rec.replay(now)
+        prep.refreshed()                                      # (the replayed refresh re-recorded the tier events: every reader waits again)
+        restore(ent.views, ent.acts)
+        self.stats["replayed"] += 1
+        if pk is not None:
+            pk.after_step(main)
+            if pk.done:
+                ent.release(sess)
 
 
 # Entries of include/frcnn_hip.h WITHOUT a trailing `void* stream` (tests/test_replay_cpu.py checks the two sets against the header):

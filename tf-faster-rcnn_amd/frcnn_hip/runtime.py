@@ -11,7 +11,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, replay
 
 
 class VarSpec(object):
@@ -33,7 +33,7 @@ class VariableStore(object):
         self.h2 = {}                                    # (filter address, shape) -> ((fp16 planes, w_inv), filter): frcnn_gemm_h2 operands
         self.h2_spread = {}                             # scope -> h2_channel_spread (host statistic of the filter)
         self.conv_info = {}                             # scope -> {w (folded, device), b, scale (np or None), bn}
-        self.graphs = {}
+        self.graphs = {}                                # key -> replay.Entry: captured TEST-mode graphs and recorded training steps
         self.seed = seed
         self.device_filters_moved = False               # a solver updated the device filters in place: the host variables are older (TrainState)
         self.derived_gen = 0                            # bumped whenever a derived filter image is ADDED or the set is dropped (derived_generation)
@@ -95,8 +95,10 @@ class VariableStore(object):
     def _drop_derived(self):
         """Everything computed FROM the variables: packed device images, pre-split x3 / h2 filter planes, captured graphs and (Session)
         the prepared-filter plan whose closures hold the filter tensors -- a direct load / restore between training steps must not leave
-        the data-gradient chain reading flipped / Winograd / h2 filters derived from tensors that were just dropped."""
-        for d in (self.packed, self.x3, self.h2, self.h2_spread, self.graphs):
+        the data-gradient chain reading flipped / Winograd / h2 filters derived from tensors that were just dropped.  The graphs and
+        recordings go through replay.release_entries: a stream search that was running on one of them ends with it."""
+        replay.release_entries(self)
+        for d in (self.packed, self.x3, self.h2, self.h2_spread):
             d.clear()
         self.derived_gen += 1
         self.device_filters_moved = False               # (the device images are rebuilt from the host variables from here on)
@@ -337,10 +339,10 @@ class Session(VariableStore):
 
     def derived_generation(self):
         """Identifies the SET of filter images derived from the variables: the session's cached operand planes / Winograd filters
-        (h2, x3, ("wino", ...)) and the prepared-filter plan.  A recorded training step (lib/nets/network.py _train_step_replayed) re-derives
+        (h2, x3, ("wino", ...)) and the prepared-filter plan.  A recorded training step (frcnn_hip/replay.py StepReplayer) re-derives
         exactly the set that existed when it was recorded; an entry added later -- a TEST-mode network first run on the shared session, another
         image shape's plan key -- would never be refreshed by its replays while ready / ready_version keep reporting it current.  The
-        recording stores this value and is dropped when it no longer matches."""
+        entry (replay.RecordedStep.gen) stores this value, and its recording is dropped when it no longer matches."""
         return (self.derived_gen, self.prepared.gen)
 
     # ---- buffers: per session, or per image shape -------------------------------------------------------------------------------------
@@ -380,18 +382,15 @@ class Session(VariableStore):
 
     def shape_scope(self, key, group=None, cap=None):
         """`with sess.shape_scope(key, group, cap):` -- buffers requested inside belong to `key` (an image shape's graph key / recorded-step
-        key).  At most `cap` scopes of a group stay alive; the least recently entered ones go first, with their sess.graphs entry."""
+        key).  At most `cap` scopes of a group stay alive; the least recently entered ones go first, with every sess.graphs entry
+        (replay.Entry) that names them as its .scope."""
         return Session._Scope(self, key, group, cap)
 
     def drop_scope(self, key):
-        """Forget one shape: its captured graph / recording (sess.graphs[key]) and every buffer registered under it.  The caller makes sure
-        nothing that addresses them is still running (shape_scope synchronises before an eviction)."""
-        for k, ent in list(self.graphs.items()):          # the shape's own graph, and every recorded step that addresses its buffers
-            if k == key or (isinstance(ent, dict) and ent.get("scope") == key):
-                pk = ent.get("picker") if isinstance(ent, dict) else None
-                if pk is not None and not pk.done:
-                    self.picking = False                  # (a stream search that was running on the dropped recording ends with it)
-                del self.graphs[k]
+        """Forget one shape: every entry of sess.graphs whose .scope it is (replay.Entry: the shape's captured graphs, the recorded steps
+        that address its buffers; released, so a stream search running on one ends with it) and every buffer registered under it.  The
+        caller makes sure nothing that addresses them is still running (shape_scope synchronises before an eviction)."""
+        replay.release_entries(self, [k for k, ent in self.graphs.items() if ent.scope == key])
         self.scope_group.pop(key, None)
         return self.scopes.pop(key, None) is not None
 
@@ -536,7 +535,8 @@ class Session(VariableStore):
         torch.cuda.current_stream(self.device).synchronize()
 
     def close(self):
-        for d in (self.graphs, self.scopes, self.scope_group, self.buffers, self.packed, self.x3, self.h2):
+        replay.release_entries(self)
+        for d in (self.scopes, self.scope_group, self.buffers, self.packed, self.x3, self.h2):
             d.clear()
 
 

@@ -15,7 +15,7 @@ import collections
 import numpy as np
 import torch
 
-from frcnn_hip import ACT_NONE, ACT_RELU, NMS_RULE_CPU, NMS_RULE_GPU, forward, ops
+from frcnn_hip import ACT_NONE, ACT_RELU, NMS_RULE_CPU, NMS_RULE_GPU, forward, ops, replay
 from frcnn_hip.runtime import VarSpec
 from model.config import cfg
 
@@ -39,8 +39,9 @@ class Network(object):
         self._requires_grad = set()
         self._gt_boxes = None
         self._sample_seed = 0
-        self.replay_stats = dict(eager=0, recorded=0, replayed=0)      # train_step_async under cfg.HIP.TRAIN_REPLAY
-        self._replay_clock, self._train_arena, self._train_scope_key = 0, None, None     # LRU clock of the recordings, replay.Arena, the step's shape scope
+        self._replayer = replay.StepReplayer()             # train_step_async under cfg.HIP.TRAIN_REPLAY
+        self.replay_stats = self._replayer.stats       # dict(eager, recorded, replayed)
+        self._train_scope_key = None                   # the step's shape scope (_train_scope)
         self._train_state = None               # the solver handle of the last train_step_with_summary (get_summary's regulariser term)
         self._fuse_tail_entry = False          # TEST-only graph restructuring, see resnetv1._fused_tail_entry
         self._plan, self._forms = None, None   # the last graph build's forward.Plan and forward.Forms (_plan_context)
@@ -573,31 +574,23 @@ class Network(object):
         sess.prepared.wait_planes()                    # a solver sharing the session re-derives filter planes on a side stream (a replay reads them)
         ops.ws_scope = self._tag                       # scratch buffers are per network tag (= per stream)
         key = self.graph_key(image_d.shape, self._im_info)
-        cur = torch.cuda.current_stream(sess.device)
         with self.shape_scope(sess, image_d.shape, self._im_info):
             if not use_graph or sess.profile is not None:
                 sess.flops_last_forward = 0
                 self._build_network(self._mode == "TRAIN")
                 return self._predictions
-            if key not in sess.graphs:
-                with torch.cuda.stream(sess.stream):
-                    sess.stream.wait_stream(cur)
-                    sess.flops_last_forward = 0
-                    self._build_network(False)                   # warm-up: allocates buffers, packs weights
-                    sess.stream.synchronize()
-                    flops = sess.flops_last_forward
-                    g = ops.Graph().capture(lambda: self._build_network(False))
-                    sess.stream.synchronize()
-                sess.graphs[key] = (g, dict(self._predictions), self._num_rois, flops, self._rois_per_image, image_d)
-            g, preds, num, flops, per, captured = sess.graphs[key]
-            self._predictions, self._num_rois, sess.flops_last_forward, self._rois_per_image = dict(preds), num, flops, per
-            if captured.data_ptr() != image_d.data_ptr():
-                # the graph reads the image at the address it was captured with; a caller that staged this image somewhere else (its own
-                # buffer, the session-wide staging buffer vs. the shape scope's) gets it copied there first -- 4 B per pixel and channel,
-                # device to device, on the stream the graph is launched on
-                captured.copy_(image_d, non_blocking=True)
-            g.launch()
+            replay.launch_captured(sess, key, key, lambda: self._build_network(False), image_d,
+                                   lambda out: (self._rois_per_image, (dict(self._predictions), self._num_rois)), self._restore_forward)
         return self._predictions
+
+    def _restore_forward(self, ent):
+        """what a replay of a captured forward_device chain leaves on the network and the session (replay.launch_captured)"""
+        preds, self._num_rois = ent.state
+        self._predictions, self._sess.flops_last_forward, self._rois_per_image = dict(preds), ent.flops, ent.per
+
+    def _restore_proposals(self, ent):
+        """... and of a captured propose_device chain (ent.state: the (rois, roi_scores, num_rois) it returns)"""
+        self._num_rois, self._sess.flops_last_forward, self._rois_per_image = ent.state[2], ent.flops, ent.per
 
     def _build_proposals(self):
         """_build_network_impl up to the proposals: head, anchors, _region_proposal -> (rois, roi_scores, num_rois int32 [B])"""
@@ -628,27 +621,12 @@ class Network(object):
         ops.ws_scope = self._tag
         scope_key = self.graph_key(image_d.shape, self._im_info)
         key = ("propose",) + scope_key
-        cur = torch.cuda.current_stream(sess.device)
         with self.shape_scope(sess, image_d.shape, self._im_info):
             if not use_graph or sess.profile is not None or cfg.TEST.MODE != "nms":
                 sess.flops_last_forward = 0
                 return self._build_proposals()
-            ent = sess.graphs.get(key)
-            if ent is None:
-                with torch.cuda.stream(sess.stream):
-                    sess.stream.wait_stream(cur)
-                    sess.flops_last_forward = 0
-                    out = self._build_proposals()                # warm-up: allocates buffers, packs weights
-                    sess.stream.synchronize()
-                    flops = sess.flops_last_forward
-                    g = ops.Graph().capture(self._build_proposals)
-                    sess.stream.synchronize()
-                ent = sess.graphs[key] = dict(scope=scope_key, graph=g, out=out, flops=flops, per=self._rois_per_image, image=image_d)
-            self._num_rois, sess.flops_last_forward, self._rois_per_image = ent["out"][2], ent["flops"], ent["per"]
-            if ent["image"].data_ptr() != image_d.data_ptr():
-                ent["image"].copy_(image_d, non_blocking=True)   # (as forward_device: the graph reads the image where it was captured)
-            ent["graph"].launch()
-        return ent["out"]
+            return replay.launch_captured(sess, key, scope_key, self._build_proposals, image_d,
+                                          lambda out: (self._rois_per_image, out), self._restore_proposals).state
 
     # only useful during testing mode
     def extract_head(self, sess, image):
@@ -747,7 +725,11 @@ class Network(object):
             self.configure_train_op(train_op)                # before the recording's key: replay_signature() carries what this sets
             if not cfg.HIP.TRAIN_REPLAY:
                 return self._train_step_body(sess, train_op, sess.buf(self._tag + "/train/losses", (5,))).clone()
-            return self._train_step_replayed(sess, train_op)
+            return self._replayer.step(sess, torch.cuda.current_stream(sess.device), self._tag + "/train", self._replay_key(train_op),
+                                       self._train_scope_key, body=lambda out: self._train_step_body(sess, train_op, out),
+                                       ready=lambda: bool(train_op.params) and train_op._sgd_table is not None,
+                                       snapshot=self._step_views, restore=self._replayed_step,
+                                       now=dict(seed=self._sample_seed, gt=int(self._gt_boxes.shape[0])), hip=cfg.HIP, cap=self.REPLAY_CAP)
 
     def _train_scope(self, sess, blobs):
         """A roidb's images differ in size from step to step (lib/roi_data_layer/layer.py:80-93); the step's activations, gradients, arena
@@ -784,115 +766,27 @@ class Network(object):
 
     REPLAY_CAP = 16             # recorded steps kept per session (one per image shape; least recently used goes first)
 
-    def _train_step_replayed(self, sess, train_op):
-        import frcnn_hip
-        from frcnn_hip import replay
-        main = torch.cuda.current_stream(sess.device)
+    def _replay_key(self, train_op):
+        """Everything a recorded step depends on besides the image's values (formed after configure_train_op)."""
         hip = tuple((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in sorted(cfg.HIP.items()))
         t = cfg.TRAIN
-        key = ("train_replay", self._tag, tuple(self._image.shape), self._im_info, int(self._gt_boxes.data_ptr()), float(train_op.lr),
-               id(train_op), train_op.replay_signature(), hip, self._num_classes, self._anchor_scales, self._anchor_ratios, bool(cfg.RESNET.MAX_POOL),
-               bool(cfg.USE_GPU_NMS), bool(cfg.USE_E2E_TF), cfg.POOLING_SIZE, cfg.POOLING_MODE,
-               (t.RPN_PRE_NMS_TOP_N, t.RPN_POST_NMS_TOP_N, t.RPN_NMS_THRESH, t.BATCH_SIZE, t.FG_FRACTION, t.FG_THRESH, t.BG_THRESH_HI, t.BG_THRESH_LO,
-                t.RPN_BATCHSIZE, t.RPN_FG_FRACTION, t.RPN_POSITIVE_OVERLAP, t.RPN_NEGATIVE_OVERLAP, bool(t.RPN_CLOBBER_POSITIVES),
-                float(t.RPN_POSITIVE_WEIGHT), tuple(t.RPN_BBOX_INSIDE_WEIGHTS), tuple(t.BBOX_INSIDE_WEIGHTS), bool(t.USE_GT),
-                tuple(float(v) for v in t.BBOX_NORMALIZE_MEANS), tuple(float(v) for v in t.BBOX_NORMALIZE_STDS)))
-        ent = sess.graphs.get(key)
-        if ent is None:
-            live = [k for k in sess.graphs if isinstance(k, tuple) and k and k[0] == "train_replay"]
-            if len(live) >= self.REPLAY_CAP:
-                self._drop_recording(sess, min(live, key=lambda k: sess.graphs[k]["used"]))
-            ent = sess.graphs[key] = dict(seen=0, rec=None, used=0, scope=self._train_scope_key)
-        self._replay_clock += 1
-        ent["used"] = self._replay_clock
-        out = sess.buf(self._tag + "/train/losses", (5,))
-        rec = ent["rec"]
-        if rec is not None and ent.get("gen") != sess.derived_generation():
-            # the set of derived filter images changed after the recording (a TEST-mode network's first run on this session, another
-            # shape's plan key): its refresh launches no longer cover the set -> this step runs eagerly (weights_changed + refresh see
-            # everything) and the shape is recorded again at its next steady step
-            self._forget_recording(sess, ent)
-            rec = None
-        if rec is not None:
-            # which physical stream every helper slot runs on: inherited from the recording, or (cfg.HIP.TRAIN_PICK_STREAMS = pool size)
-            # searched once per session by timing real steps (replay.StreamPicker) and then shared by every recording with the same slots
-            pk = ent.get("picker")
-            picked = sess.picked_streams
-            if pk is None and int(cfg.HIP.TRAIN_PICK_STREAMS) > 0 and picked is None and not sess.picking:
-                pool = [torch.cuda.Stream(device=sess.device) for _ in range(int(cfg.HIP.TRAIN_PICK_STREAMS))]
-                pk = ent["picker"] = replay.StreamPicker(rec, main, pool)
-                sess.picking = True
-            if pk is not None and not pk.done:
-                pk.before_step(main)
-                if pk.done:                                       # (nothing to try)
-                    sess.picked_streams, sess.picking, sess.pick_log = list(pk.best[1:]), False, list(pk.log)
-            if pk is None or pk.done:
-                helpers = picked if (picked is not None and len(picked) == len(rec.streams) - 1) else list(rec.streams[1:])
-                if rec.bound is None or [int(x.cuda_stream) for x in rec.bound] != [int(x.cuda_stream) for x in [main] + helpers]:
-                    rec.bind([main] + helpers)
-            for h, st in list(sess.prepared.readers.items()):     # a TEST-mode network on another stream read the filter images since the
-                if h != int(main.cuda_stream):                    # last refresh: the list's refresh waits for `main` only, so main waits for it
-                    main.wait_stream(st)
-            sess.prepared.readers = {}
-            rec.replay(dict(seed=self._sample_seed, gt=int(self._gt_boxes.shape[0])))
-            sess.prepared.refreshed()                         # (the replayed refresh re-recorded the tier events: every reader waits again)
-            self._predictions, self._losses, self._proposal_targets, self._anchor_targets = ent["views"]
-            self._act_summaries = ent["acts"]
-            self._sample_seed += 2
-            self.replay_stats["replayed"] += 1
-            if pk is not None and not pk.done:
-                pk.after_step(main)
-                if pk.done:
-                    sess.picked_streams, sess.picking, sess.pick_log = list(pk.best[1:]), False, list(pk.log)
-            return out.clone()
-        arena = self._train_arena
-        if arena is None or arena.sess is not sess:
-            arena = self._train_arena = replay.Arena(sess, self._tag + "/train")
-        arena.reset()
-        prep = sess.prepared
-        steady = (ent["seen"] >= 1 and bool(train_op.params) and train_op._sgd_table is not None
-                  and frcnn_hip.recorder is None
-                  and (not cfg.HIP.PREP_STREAM or (prep.ready_version == prep.version and len(prep.plan) > 0 and len(prep.ready) == len(prep.plan))))
-        gen_before = sess.derived_generation()
-        ops.arena = arena
-        try:
-            if steady:
-                prep.forget_waits(main)                       # the recorded step carries every tier's wait at its first use
-                rec = replay.Recording(main)
-                rec.vars = dict(seed=self._sample_seed, gt=int(self._gt_boxes.shape[0]))
-                frcnn_hip.recorder = rec
-            self._train_step_body(sess, train_op, out)
-        finally:
-            ops.arena = None
-            frcnn_hip.recorder = None
-        ent["seen"] += 1
-        if steady and sess.derived_generation() == gen_before:     # (a filter image derived inline during the step = not the steady state yet)
-            ent["rec"] = rec
-            ent["gen"] = gen_before
-            ent["views"] = (dict(self._predictions), dict(self._losses), dict(self._proposal_targets), dict(self._anchor_targets))
-            ent["acts"] = list(self._act_summaries)
-            self.replay_stats["recorded"] += 1
-        else:
-            self.replay_stats["eager"] += 1
-        return out.clone()
+        return ("train_replay", self._tag, tuple(self._image.shape), self._im_info, int(self._gt_boxes.data_ptr()), float(train_op.lr),
+                id(train_op), train_op.replay_signature(), hip, self._num_classes, self._anchor_scales, self._anchor_ratios, bool(cfg.RESNET.MAX_POOL),
+                bool(cfg.USE_GPU_NMS), bool(cfg.USE_E2E_TF), cfg.POOLING_SIZE, cfg.POOLING_MODE,
+                (t.RPN_PRE_NMS_TOP_N, t.RPN_POST_NMS_TOP_N, t.RPN_NMS_THRESH, t.BATCH_SIZE, t.FG_FRACTION, t.FG_THRESH, t.BG_THRESH_HI, t.BG_THRESH_LO,
+                 t.RPN_BATCHSIZE, t.RPN_FG_FRACTION, t.RPN_POSITIVE_OVERLAP, t.RPN_NEGATIVE_OVERLAP, bool(t.RPN_CLOBBER_POSITIVES),
+                 float(t.RPN_POSITIVE_WEIGHT), tuple(t.RPN_BBOX_INSIDE_WEIGHTS), tuple(t.BBOX_INSIDE_WEIGHTS), bool(t.USE_GT),
+                 tuple(float(v) for v in t.BBOX_NORMALIZE_MEANS), tuple(float(v) for v in t.BBOX_NORMALIZE_STDS)))
 
-    @staticmethod
-    def _forget_recording(sess, ent):
-        """Drops an entry's recording (kept: its `seen` count, so the next steady step records again).  A stream search that was running on
-        this recording ends with it -- sess.picking must not stay set, or no other recording could ever start one."""
-        pk = ent.pop("picker", None)
-        if pk is not None and not pk.done:
-            sess.picking = False
-        ent["rec"] = None
-        ent.pop("views", None)
-        ent.pop("acts", None)
-        ent.pop("gen", None)
+    def _step_views(self):
+        """what a recorded step left on the network for its readers (replay.StepReplayer: snapshot) ..."""
+        return (dict(self._predictions), dict(self._losses), dict(self._proposal_targets), dict(self._anchor_targets)), list(self._act_summaries)
 
-    @classmethod
-    def _drop_recording(cls, sess, key):
-        """LRU eviction of a recorded step (REPLAY_CAP)."""
-        cls._forget_recording(sess, sess.graphs[key])
-        del sess.graphs[key]
+    def _replayed_step(self, views, acts):
+        """... and what a replayed step owes them: the same views, and the seed advance of _train_step_body"""
+        self._predictions, self._losses, self._proposal_targets, self._anchor_targets = views
+        self._act_summaries = acts
+        self._sample_seed += 2
 
     @staticmethod
     def configure_train_op(train_op):

@@ -642,6 +642,22 @@ int frcnn_softmax_ce_loss(const float* logits_d, const float* labels_d, int R, i
 int frcnn_smooth_l1_loss(const float* pred_d, const float* targets_d, const float* inside_w_d, const float* outside_w_d,
                          long long n, float sigma, float mean_divisor, float* loss_d, float* dpred_d, void* ws,
                          size_t ws_bytes, void* stream);
+/* IoU-family box regression losses on the decoded boxes (csrc/iouloss_math.h states the rule): pred, targets, inside_w, outside_w all
+ * [N, 4K]; a slice (four columns 4k..4k+3 of a row) is active iff any of its inside weights is non-zero, its weight is outside_w[r, 4k].
+ * refs [N, ref_cols]: the row's reference box (ref_cols 4: x1,y1,x2,y2 -- an anchor; 5: the box in columns 1..4 -- a RoI).  pred * std +
+ * mean and targets * std + mean are decoded on it as bbox_transform_inv does (widths clamped at log(1000/16)); kind 1 IoU, 2 GIoU, 3
+ * DIoU, 4 CIoU (alpha constant in the gradient), plain areas, eps 1e-7.  loss_d[0] = weight / mean_divisor * sum(ow * L) over the
+ * active slices; dpred_d [N, 4K] gets every element written (+0 in inactive slices).  Each slice in double, rounded once; a fixed order
+ * of additions, no atomics, nothing allocated, the same bits on every run and from the host entry.  FRCNN_E_ARG: a null pointer,
+ * N <= 0, K <= 0, ref_cols not 4 or 5, kind not in 1..4, a std that is not positive, mean_divisor <= 0, a weight that is not finite;
+ * then FRCNN_E_UNSUPPORTED for N * K >= 2^31, then FRCNN_E_WS for a short workspace. */
+size_t frcnn_iou_loss_workspace_bytes(long long slices);
+int frcnn_iou_loss(const float* pred_d, const float* targets_d, const float* inside_w_d, const float* outside_w_d, long long N, int K,
+                   const float* refs_d, int ref_cols, const float* means, const float* stds, int kind, float weight, float mean_divisor,
+                   float* loss_d, float* dpred_d, void* ws, size_t ws_bytes, void* stream);
+int frcnn_iou_loss_host(const float* pred, const float* targets, const float* inside_w, const float* outside_w, long long N, int K,
+                        const float* refs, int ref_cols, const float* means, const float* stds, int kind, float weight, float mean_divisor,
+                        float* loss, float* dpred);
 
 /* ---- backward pass + solver (lib/model/train_val.py:116-153) ------------------ */
 /* Operand re-layouts that let frcnn_conv2d_nhwc compute conv gradients (see csrc/backward_kernels.hip):

@@ -149,6 +149,9 @@ SIGNATURES = {
     "frcnn_loss_workspace_bytes": (c_size_t, [c_longlong]),
     "frcnn_softmax_ce_loss": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "frcnn_smooth_l1_loss": (c_int, [_P, _P, _P, _P, c_longlong, c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    "frcnn_iou_loss_workspace_bytes": (c_size_t, [c_longlong]),
+    "frcnn_iou_loss": (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P, c_int, _P, _P, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    "frcnn_iou_loss_host": (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P, c_int, _P, _P, c_int, c_float, c_float, _P, _P]),
     "frcnn_transpose_pad": (c_int, [_P, c_int, c_int, _P, c_int, _P]),
     "frcnn_im2col_t": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "frcnn_flip_transpose_filter": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),

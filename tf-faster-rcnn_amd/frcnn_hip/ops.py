@@ -1349,6 +1349,62 @@ def smooth_l1_loss(pred, targets, inside_w, outside_w, sigma, mean_divisor):
     return loss, grad
 
 
+IOU_LOSS_KINDS = {"iou": 1, "giou": 2, "diou": 3, "ciou": 4}      # IOULOSS_* of csrc/iouloss_math.h
+
+
+def _iou_loss_kind(kind):
+    if kind in IOU_LOSS_KINDS:
+        return IOU_LOSS_KINDS[kind]
+    if isinstance(kind, str):
+        raise ValueError("iou_loss: kind %r is none of %s" % (kind, sorted(IOU_LOSS_KINDS)))
+    return int(kind)
+
+
+def _host_floats(values):
+    a = np.ascontiguousarray(values, dtype=np.float32)
+    if _binding.recorder is not None:
+        _binding.recorder.keep.append(a)         # (a recorded launch keeps the pointer)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def iou_loss(pred, targets, inside_w, outside_w, refs, means, stds, kind, weight, mean_divisor, K):
+    """IoU / GIoU / DIoU / CIoU loss on the decoded boxes (frcnn_iou_loss, csrc/iouloss_math.h): pred, targets, inside_w, outside_w of one
+    shape with 4 K N elements, read as [N, 4K]; refs [N,4] (anchors) or [N,5] (RoIs); means / stds four floats each; kind a name of
+    IOU_LOSS_KINDS or its number.  -> (loss [1], grad like pred, every element written)."""
+    _chk(pred), _chk(targets), _chk(inside_w), _chk(outside_w), _chk(refs)
+    dev, K = pred.device, int(K)
+    if K <= 0 or pred.numel() % (4 * K) or not (targets.numel() == inside_w.numel() == outside_w.numel() == pred.numel()):
+        raise ValueError("iou_loss: pred, targets and the weights must have the same number of elements, a multiple of 4 K")
+    N = pred.numel() // (4 * K)
+    if refs.dim() != 2 or refs.shape[0] != N or len(means) != 4 or len(stds) != 4:
+        raise ValueError("iou_loss: refs must have one row per row of pred (%d), means and stds four values" % N)
+    loss = _zeros((1,), dtype=torch.float32, device=dev)
+    grad = _empty(tuple(pred.shape), dtype=pred.dtype, device=dev)
+    ws = workspace(lib().frcnn_iou_loss_workspace_bytes(N * K), dev, "iou_loss")
+    m, s = _host_floats(means), _host_floats(stds)
+    call("frcnn_iou_loss", _ptr(pred), _ptr(targets), _ptr(inside_w), _ptr(outside_w), N, K, _ptr(refs), int(refs.shape[1]), m[1], s[1],
+         _iou_loss_kind(kind), float(weight), float(mean_divisor), _ptr(loss), _ptr(grad), _ptr(ws), ws.numel(), _stream())
+    return loss, grad
+
+
+def iou_loss_host(pred, targets, inside_w, outside_w, refs, means, stds, kind, weight, mean_divisor, K):
+    """frcnn_iou_loss_host: the same on HOST numpy arrays, no GPU needed.  -> (loss [1], grad like pred) as numpy arrays."""
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    pred, targets, inside_w, outside_w, refs = f32(pred), f32(targets), f32(inside_w), f32(outside_w), f32(refs)
+    K = int(K)
+    if K <= 0 or pred.size % (4 * K) or not (targets.size == inside_w.size == outside_w.size == pred.size):
+        raise ValueError("iou_loss_host: pred, targets and the weights must have the same number of elements, a multiple of 4 K")
+    N = pred.size // (4 * K)
+    if refs.ndim != 2 or refs.shape[0] != N or len(means) != 4 or len(stds) != 4:
+        raise ValueError("iou_loss_host: refs must have one row per row of pred (%d), means and stds four values" % N)
+    m, s = f32(means), f32(stds)
+    loss, grad = np.zeros(1, np.float32), np.empty(pred.shape, np.float32)
+    check(lib().frcnn_iou_loss_host(pred.ctypes.data, targets.ctypes.data, inside_w.ctypes.data, outside_w.ctypes.data, N, K, refs.ctypes.data,
+                                    int(refs.shape[1]), m.ctypes.data, s.ctypes.data, _iou_loss_kind(kind), float(weight), float(mean_divisor),
+                                    loss.ctypes.data, grad.ctypes.data), "frcnn_iou_loss_host")
+    return loss, grad
+
+
 # ------------------------------------------------------------------------------------------ backward
 def transpose_pad(x2d, Mp, out=None):
     """x2d [M,C] -> [C,Mp] (zero padded)."""

@@ -415,4 +415,5 @@ HOST_ONLY = frozenset(["frcnn_generate_anchors", "frcnn_winograd_filter_transfor
                        "frcnn_jpeg_quant_tables", "frcnn_jpeg_coefs_host", "frcnn_jpeg_stream_bound", "frcnn_jpeg_entropy_encode",
                        "frcnn_draw_detections_host", "frcnn_proposal_recall_host", "frcnn_soft_nms_host",
                        "frcnn_box_vote_host", "frcnn_merge_flip_views_host",
-                       "frcnn_roi_align_host", "frcnn_roi_align_bwd_host", "frcnn_roi_align_classify_host", "frcnn_ohem_select_host"])
+                       "frcnn_roi_align_host", "frcnn_roi_align_bwd_host", "frcnn_roi_align_classify_host", "frcnn_ohem_select_host",
+                       "frcnn_iou_loss_host"])

@@ -165,6 +165,15 @@ __C = AttrDict(
     # FG_THRESH / BG_THRESH_HI / BG_THRESH_LO still say which proposals are foreground, background or neither.  TRAIN.USE_GT is refused with
     # it.  Selected on the device, so TRAIN_REPLAY stays; part of the recorded-step key like every HIP key.  False, the default: exactly the
     # launches the step always made.  Cost (about one more tail forward over all proposals): profiles/ohem.txt.
+    # BBOX_LOSS / RPN_BBOX_LOSS: the box regression loss of the RCNN head / of the RPN in the training step: 'smooth_l1', the default, the
+    # reference's loss on the encoded deltas and exactly the launches the step always made; 'iou', 'giou' (Rezatofighi et al. 2019), 'diou'
+    # or 'ciou' (Zheng et al. 2020): the loss on the DECODED boxes (csrc/iouloss_math.h, frcnn_iou_loss) -- prediction and target are decoded
+    # on the row's RoI (head, with TRAIN.BBOX_NORMALIZE_MEANS / STDS undone) or anchor (RPN), 1 - IoU plus the kind's penalty, summed over
+    # the slices whose inside weights are not all zero, times the outside weight, divided by the rows (head) or 1 (RPN) as smooth-L1 is.  An
+    # IoU loss has no per-coordinate weight: the INSIDE_WEIGHTS only mark the active slices.  BBOX_LOSS_WEIGHT / RPN_BBOX_LOSS_WEIGHT
+    # multiply that loss and its gradient (finite and > 0; read only when the matching loss is not 'smooth_l1').  HIP.OHEM ranks RoIs by the
+    # smooth-L1 loss, so it is refused with another BBOX_LOSS; any RPN_BBOX_LOSS goes with it.  Part of the recorded-step key like every HIP
+    # key; a snapshot does not record the loss it was trained with.  Cost: profiles/iou_loss.txt.
     HIP=dict(WINOGRAD=True, WINOGRAD_MIN_CIN=64, WINOGRAD_M=4, WINOGRAD_F2_SCOPES=("block1", "block2"), WINOGRAD_DIRECT_SCOPES=(),
              WINOGRAD_TRAIN=True, WINOGRAD_DGRAD=True,
              WINOGRAD_7X7=True, WINOGRAD_FUSED_F2=True, FUSE_TAIL_MEAN=True, MFMA_X3=True,
@@ -172,7 +181,8 @@ __C = AttrDict(
              X3_TILE_CFG=-1, H2_TRAIN=True, WGRAD_STREAM=2, WGRAD_TN=True, WGRAD_H2=True, PREP_STREAM=True, TRAIN_REPLAY=True, TRAIN_PICK_STREAMS=6,
              GRAPH_CACHE_SHAPES=4, TRAIN_CACHE_SHAPES=16, JPEG_DEVICE=False, TEST_BATCH_IMAGES=1,
              SOFT_NMS=0, SOFT_NMS_SIGMA=0.5, SOFT_NMS_MIN_SCORE=0.001, TEST_FLIP=False, BBOX_VOTE=False, BBOX_VOTE_THRESH=0.8,
-             ROI_ALIGN_SAMPLES=2, OHEM=False, OHEM_NMS_THRESH=0.7))
+             ROI_ALIGN_SAMPLES=2, OHEM=False, OHEM_NMS_THRESH=0.7,
+             BBOX_LOSS='smooth_l1', RPN_BBOX_LOSS='smooth_l1', BBOX_LOSS_WEIGHT=1.0, RPN_BBOX_LOSS_WEIGHT=1.0))
 
 
 def pooling_description(c=None):
@@ -190,6 +200,20 @@ def ohem_description(c=None):
         return None
     nms = "NMS at %g" % c.HIP.OHEM_NMS_THRESH if float(c.HIP.OHEM_NMS_THRESH) > 0 else "no NMS"
     return "RoI minibatch: online hard example mining, the %d hardest of %d proposals (%s)" % (c.TRAIN.BATCH_SIZE, c.TRAIN.RPN_POST_NMS_TOP_N, nms)
+
+
+BOX_LOSSES = ('smooth_l1', 'iou', 'giou', 'diou', 'ciou')
+
+
+def box_loss_description(c=None):
+    """One line for the training tool's log when a box regression loss is not smooth-L1 (None otherwise)."""
+    c = __C if c is None else c
+    if c.HIP.BBOX_LOSS == 'smooth_l1' and c.HIP.RPN_BBOX_LOSS == 'smooth_l1':
+        return None
+    part = lambda name, w: name if name == 'smooth_l1' else "%s on the decoded boxes (weight %g)" % (name, w)
+    return ("Box regression loss: head %s, RPN %s; an IoU loss has no per-coordinate weight, BBOX_INSIDE_WEIGHTS only mark the active "
+            "slices; a snapshot does not record the loss it was trained with"
+            % (part(c.HIP.BBOX_LOSS, c.HIP.BBOX_LOSS_WEIGHT), part(c.HIP.RPN_BBOX_LOSS, c.HIP.RPN_BBOX_LOSS_WEIGHT)))
 
 
 __C.DATA_DIR = osp.abspath(osp.join(__C.ROOT_DIR, 'data'))

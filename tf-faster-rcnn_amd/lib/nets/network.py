@@ -25,6 +25,7 @@ class Network(object):
         self._predictions = {}
         self._losses = {}
         self._anchor_targets = {}
+        self._rpn_anchors = None               # cfg.HIP.RPN_BBOX_LOSS other than 'smooth_l1': the [H W A, 4] anchors the last step's loss decoded on
         self._proposal_targets = {}
         self._layers = {}
         self._act_summaries = []
@@ -302,10 +303,26 @@ class Network(object):
         p, at, pt = self._predictions, self._anchor_targets, self._proposal_targets
         _, H, W, _ = p["rpn_cls_score"].shape
         rpn_ce, g_rpn_cls = ops.softmax_ce_loss(p["rpn_cls_score"], at["rpn_labels"], rpn_shape=(A, H, W))
-        rpn_box, g_rpn_box = self._smooth_l1_loss(p["rpn_bbox_pred"], at["rpn_bbox_targets"], at["rpn_bbox_inside_weights"],
-                                                  at["rpn_bbox_outside_weights"], sigma=sigma_rpn, dim=[1, 2, 3])
+        h, t = cfg.HIP, cfg.TRAIN
+        if h.RPN_BBOX_LOSS == "smooth_l1":
+            rpn_box, g_rpn_box = self._smooth_l1_loss(p["rpn_bbox_pred"], at["rpn_bbox_targets"], at["rpn_bbox_inside_weights"],
+                                                      at["rpn_bbox_outside_weights"], sigma=sigma_rpn, dim=[1, 2, 3])
+        else:
+            # csrc/iouloss_math.h on the anchors the anchor target layer encoded against (it builds them in-kernel from the same base
+            # anchors): [1,H,W,4A] read as [H W A, 4], RPN targets are not normalised, batch of 1 like dim=[1, 2, 3] above
+            # (kept beside the targets, not among them: _anchor_targets is what the score summaries list)
+            self._rpn_anchors = ops.generate_anchors_pre(H, W, self._feat_stride[0], self._base_anchors)
+            rpn_box, g_rpn_box = ops.iou_loss(p["rpn_bbox_pred"], at["rpn_bbox_targets"], at["rpn_bbox_inside_weights"],
+                                              at["rpn_bbox_outside_weights"], self._rpn_anchors, (0.0, 0.0, 0.0, 0.0), (1.0, 1.0, 1.0, 1.0),
+                                              h.RPN_BBOX_LOSS, float(h.RPN_BBOX_LOSS_WEIGHT), 1.0, 1)
         ce, g_cls = ops.softmax_ce_loss(p["cls_score"], pt["labels"].view(-1))
-        box, g_box = self._smooth_l1_loss(p["bbox_pred"], pt["bbox_targets"], pt["bbox_inside_weights"], pt["bbox_outside_weights"])
+        if h.BBOX_LOSS == "smooth_l1":
+            box, g_box = self._smooth_l1_loss(p["bbox_pred"], pt["bbox_targets"], pt["bbox_inside_weights"], pt["bbox_outside_weights"])
+        else:
+            # on the sampled RoIs, with the means / stds _proposal_target_layer normalised the targets by; the mean over the rows as above
+            box, g_box = ops.iou_loss(p["bbox_pred"], pt["bbox_targets"], pt["bbox_inside_weights"], pt["bbox_outside_weights"], pt["rois"],
+                                      t.BBOX_NORMALIZE_MEANS, t.BBOX_NORMALIZE_STDS, h.BBOX_LOSS, float(h.BBOX_LOSS_WEIGHT),
+                                      float(p["bbox_pred"].shape[0]), self._num_classes)
         self._losses = dict(cross_entropy=ce, loss_box=box, rpn_cross_entropy=rpn_ce, rpn_loss_box=rpn_box)
         self._loss_seeds = [(p["rpn_cls_score"], g_rpn_cls), (p["rpn_bbox_pred"], g_rpn_box), (p["cls_score"], g_cls),
                             (p["bbox_pred"], g_box)]
@@ -487,11 +504,22 @@ class Network(object):
             if int(t.RPN_POST_NMS_TOP_N) > Network.OHEM_MAX_ROWS or int(t.BATCH_SIZE) > Network.OHEM_MAX_ROWS:
                 bad.append("HIP.OHEM with TRAIN.RPN_POST_NMS_TOP_N = %d, TRAIN.BATCH_SIZE = %d (frcnn_ohem_select holds at most %d rows)"
                            % (int(t.RPN_POST_NMS_TOP_N), int(t.BATCH_SIZE), Network.OHEM_MAX_ROWS))
+        for key in ("BBOX_LOSS", "RPN_BBOX_LOSS"):
+            if h[key] not in Network.BOX_LOSSES:
+                bad.append("HIP.%s = %r (one of %s)" % (key, h[key], ", ".join(repr(v) for v in Network.BOX_LOSSES)))
+            elif h[key] != "smooth_l1":
+                w = h[key + "_WEIGHT"]
+                if isinstance(w, bool) or not isinstance(w, (int, float)) or not (0.0 < float(w) < float("inf")):
+                    bad.append("HIP.%s_WEIGHT = %r (must be finite and > 0)" % (key, w))
+        if h.OHEM and h.BBOX_LOSS != "smooth_l1":
+            bad.append("HIP.OHEM with HIP.BBOX_LOSS = %r (csrc/ohem_math.h ranks the RoIs by the smooth-L1 loss; mining by one loss and "
+                       "training on another is refused)" % (h.BBOX_LOSS,))
         if h.TEST_FLIP and mode == "TEST":
             bad += Network._flip_refusals()
         if bad:
             raise NotImplementedError("unsupported configuration for the HIP path: " + "; ".join(bad))
 
+    BOX_LOSSES = ("smooth_l1", "iou", "giou", "diou", "ciou")      # HIP.BBOX_LOSS / HIP.RPN_BBOX_LOSS (model.config.BOX_LOSSES)
     OHEM_MAX_ROWS = 3072                  # OHEM_MAXN of csrc/ohem_math.h: proposal rows, and rows of the batch
     FLIP_MAX_ROWS = 1024                  # rows per image and class the post-processing holds (frcnn_detect_post_*: R <= 1024)
 

@@ -21,7 +21,7 @@ import torch
 import _init_paths  # noqa: F401
 from frcnn_hip import parallel
 from frcnn_hip.runtime import Session
-from model.config import cfg, cfg_from_file, cfg_from_list, get_output_dir, get_output_tb_dir, ohem_description, pooling_description
+from model.config import box_loss_description, cfg, cfg_from_file, cfg_from_list, get_output_dir, get_output_tb_dir, ohem_description, pooling_description
 from model.train_val import filter_roidb, get_training_roidb, synthetic_data_layer, train_net
 from test_net import NETS
 
@@ -88,6 +88,8 @@ if __name__ == '__main__':
         print(pooling_description())
         if ohem_description() is not None:
             print(ohem_description())
+        if box_loss_description() is not None:
+            print(box_loss_description())
     np.random.seed(cfg.RNG_SEED)
     if args.net not in NETS:
         raise NotImplementedError(args.net)
